@@ -13,8 +13,12 @@ order (State.sum), i.e. the whole job including the final merge.  Inputs are res
 before timing starts.  Weak scaling: every rank owns its own 1e9-row shard.
 
 Prints ONE JSON line (rank 0) with `roofline` (fused scan pass vs the 8 TB/s HBM peak, timed
-with HIP events on the plan's stream) and `cpu_baseline` (the oracle's C restatement of the
-same Spark semantics on a bounded sample, on the host cores; rank 0, N = 1 only).
+with HIP events on the plan's stream in the timed steps themselves).  A plain run does only that:
+set up, warm up, time the steps, print the line.  `--full` adds what takes runs of its own:
+`cpu_baseline` (the oracle's C restatement of the same Spark semantics on a bounded sample, on
+the host cores; rank 0, N = 1 only), `scan_without_hll`, `host_ingest` and `valu_roofline` (the
+register-only hash-rate probe; C3 too).  `--dump-outputs DIR` writes the last timed step's
+results as DIR/<name>.npy, so that two builds can be compared output for output.
 """
 import argparse
 import ctypes
@@ -39,16 +43,23 @@ def parse_args():
     p.add_argument("--steps", type=int, default=10)
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--rows", type=int, default=1_000_000_000, help="rows per GPU")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what takes runs of its own beside the headline: cpu_baseline, "
+                        "scan_without_hll, host_ingest, valu_roofline (--no-cpu-baseline, --no-side-passes and "
+                        "--e2e-batch-rows 0 trim it); off by default: a plain run times the steps only")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step returned as DIR/<name>.npy "
+                        "(float64; rank 0); the inputs are seeded, so two builds compare output for output")
     p.add_argument("--cpu-sample-rows", type=int, default=256_000_000)
     p.add_argument("--cpu-threads", type=int, default=0,
                    help="0 = every CPU this process may use (sched_getaffinity, capped by OMP_NUM_THREADS: "
                         "the GPU box's host share for one GPU)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
     p.add_argument("--e2e-batch-rows", type=int, default=62_500_000,
-                   help="host-resident C2 batch streamed to 1e9 rows for the PCIe-inclusive rate (0 = skip)")
+                   help="with --full: host-resident C2 batch streamed to 1e9 rows for the PCIe-inclusive rate "
+                        "(0 = skip)")
     p.add_argument("--no-side-passes", action="store_true",
-                   help="skip the scan_without_hll pass (profiler runs: the kernel trace then "
-                        "holds only the headline launches)")
+                   help="with --full: skip the scan_without_hll and host_ingest passes")
     p.add_argument("--workload", default="c2", choices=["c1", "c2", "c3", "c4", "c5"],
                    help="c2 = the headline scan (default); c3 = HLL on 64 columns; c4 = group-by")
     p.add_argument("--c1-rows", type=int, default=10_000_000, help="rows per GPU")
@@ -67,7 +78,7 @@ def parse_args():
                    help="C4 key text: 12 decimal digits (packs into one word: 8-byte records), 'k' + 11 "
                         "digits (not a digit string: the 16-byte record path, after the packed staging gives up), "
                         "uuid (36-character UUID text of the same ids: 128-bit records, isPrimaryKey's "
-                        "shape), pair (a two-column key (int64 id / 1000, 8-digit id % 1000): 20 encoded "
+                        "shape), pair (a two-column key (int64 id / 1000, 8-digit id %% 1000): 20 encoded "
                         "bytes, the hashed record path; Uniqueness / Distinctness / UniqueValueRatio / "
                         "CountDistinct of the pair) or pair64 (the same pair as (int64, int64): 16 encoded "
                         "bytes, the 16-byte-key records)")
@@ -566,6 +577,7 @@ def run_c3(args, world, rank, local):
         return raw
     elapsed, kernel_ms, raw = _timed(args, world, step)
     est = d.ApproxCountDistinctState(list(raw[0].words)).metricValue()
+    _dump_outputs(args, rank, _states_arrays(raw, len(analyzers)))  # (before the plan's buffer is reused)
     bpr = args.c3_columns * ((4 + 16 + 1.0 / 8) if utf8 else (8 + 1.0 / 8))
     full_job = None
     if args.c3_batches > 1 and not utf8:
@@ -617,8 +629,8 @@ def run_c3(args, world, rank, local):
         "roofline": _step_roofline(bpr * args.c3_rows, kernel_ms / 1e3, "one HLL plan pass (scan kernels, HIP events)",
                                    workload=None if utf8 else "c3", default_size=args.c3_rows == 125_000_000),
         # (the register-only hash-rate probe times the 8-byte hashLong, not 16-byte strings)
-        "valu_roofline": None if utf8 else valu_roofline(local, float(args.c3_rows) * args.c3_columns,
-                                                         kernel_ms),
+        "valu_roofline": valu_roofline(local, float(args.c3_rows) * args.c3_columns, kernel_ms)
+        if args.full and not utf8 else None,
         "check": {"column0_estimate": est, "rows_column0": args.c3_rows},
         "full_job": full_job,
     }
@@ -738,6 +750,12 @@ def run_c4(args, world, rank, local):
     elapsed, _, ctx = _timed(args, world, step)
     metrics = {str(a): ctx.metric(a).value.get() for a in analyzers[:4]}
     hist = None if pair else ctx.metric(analyzers[4]).value.get()
+    if args.dump_outputs:  # the four metrics; Histogram: its bin count and the detail bins' counts, largest first
+        arrays = {"metrics": [metrics[str(a)] for a in analyzers[:4]]}
+        if hist is not None:
+            arrays["histogram"] = [float(hist.numberOfBins)] + sorted(
+                (float(v.absolute) for v in hist.values.values()), reverse=True)
+        _dump_outputs(args, rank, arrays)
     verify = None
     if args.c4_verify and world == 1:
         del ctx
@@ -938,6 +956,7 @@ def run_c1(args, world, rank, local):
         return d.AnalysisRunner.onData(data).addAnalyzers(analyzers).run()
     elapsed, _, ctx = _timed(args, world, step)
     metrics = {str(a): ctx.metric(a).value.get() for a in analyzers}
+    _dump_outputs(args, rank, {"metrics": [metrics[str(a)] for a in analyzers]})
     return {
         "metric": "rows/sec for the C1 AnalysisRunner suite (Item table)",
         "value": args.c1_rows * world * args.steps / elapsed, "unit": "rows/s", "n_gpus": world,
@@ -965,6 +984,9 @@ def run_c5(args, world, rank, local):
     elapsed, _, profiles = _timed(args, world, step)
     p = profiles.profiles
     n_hist = sum(1 for c in p.values() if c.histogram is not None)
+    if args.dump_outputs:  # per column, in name order: completeness, approximate distinct count, inferred type
+        _dump_outputs(args, rank, {"profiles": [[p[n].completeness, float(p[n].approximateNumDistinctValues),
+                                                 float(p[n].dataType)] for n in sorted(p)]})
     step_s = elapsed / args.steps
     cols = shard.columns
     # pass 1 reads every column once: Completeness, HLL, DataType and -- for schema-numeric columns
@@ -1047,6 +1069,32 @@ def _timed(args, world, step):
     except (RuntimeError, ValueError):  # the step did not record the events
         kernel_ms = None
     return elapsed, kernel_ms, out
+
+
+_STATE_FIELDS = ("kind", "has_value", "num_matches", "count", "sum", "n", "avg", "m2", "value",
+                 "y_avg", "ck", "x_mk", "y_mk")
+
+
+def _states_arrays(raw, n_ops: int):
+    """The dq_state array a plan's finish_raw returns, as float64 arrays: `states` (n_ops x the
+    scalar fields of dq_state, in _STATE_FIELDS' order; the counts are below 2^53, so exact) and
+    `hll_words` (n_ops x 104: the low and the high 32 bits of each of the 52 register words)."""
+    import numpy as np
+    states = np.array([[float(getattr(raw[i], f)) for f in _STATE_FIELDS] for i in range(n_ops)],
+                      dtype=np.float64).reshape(n_ops, len(_STATE_FIELDS))
+    words = np.array([[int(w) for w in raw[i].words] for i in range(n_ops)], dtype=np.int64).view(np.uint64)
+    halves = np.concatenate([words & np.uint64(0xFFFFFFFF), words >> np.uint64(32)], axis=1)
+    return {"states": states, "hll_words": halves.astype(np.float64)}
+
+
+def _dump_outputs(args, rank: int, arrays) -> None:
+    """--dump-outputs: rank 0 writes every array of `arrays` as DIR/<name>.npy (float64)."""
+    if not args.dump_outputs or rank != 0:
+        return
+    import numpy as np
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def _spawn_ranks(n: int) -> int:
@@ -1138,6 +1186,7 @@ def main():
     # sanity: the suite produced every state (5% NULLs -> nothing is empty)
     assert all(s is not None for s in states), "empty state in the benchmark suite"
     assert states[0].numMatches == args.rows * world
+    _dump_outputs(args, rank, _states_arrays(raw, n_ops))
 
     rows_total = args.rows * world * args.steps
     value = rows_total / elapsed
@@ -1169,14 +1218,14 @@ def main():
                           "kernel_ms": kernel_ms,
                           "algorithmic_bytes_per_launch": BYTES_PER_ROW * args.rows},
                          **({"traffic_source": traffic_src} if traffic_src else {})),
-        "valu_roofline": valu_roofline(local, float(args.rows) * n_hll, kernel_ms) if n_hll else None,
+        "valu_roofline": valu_roofline(local, float(args.rows) * n_hll, kernel_ms) if n_hll and args.full else None,
         "cpu_baseline": None,
     }
-    if rank == 0 and world == 1 and not args.no_side_passes:
+    if args.full and rank == 0 and world == 1 and not args.no_side_passes:
         result["scan_without_hll"] = scan_without_hll(table, local, args.steps)
         if args.e2e_batch_rows > 0:
             result["host_ingest"] = host_ingest(args, local)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         threads = args.cpu_threads or host_cpu_share()
         result["cpu_baseline"] = cpu_baseline(args.cpu_sample_rows, threads)
         # beside the one-GPU share: every host CPU (nproc), as SURVEY §8(d) states the baseline

@@ -27,7 +27,7 @@ if [[ $STEPS == *tests* ]]; then
   st=$?; tail -15 "$OUT/pytest_gpu_$TAG.log"; ok_or_stop $st tests 1
 fi
 if [[ $STEPS == *bench* ]]; then
-  timeout -k 10 600 python -u bench.py --steps ${BENCH_STEPS:-10} --warmup 3 ${BENCH_ARGS:-} \
+  timeout -k 10 600 python -u bench.py --full --steps ${BENCH_STEPS:-10} --warmup 3 ${BENCH_ARGS:-} \
     > "$OUT/bench_$TAG.log" 2>&1
   st=$?; tail -3 "$OUT/bench_$TAG.log"; ok_or_stop $st bench
 fi

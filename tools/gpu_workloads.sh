@@ -9,7 +9,7 @@ mkdir -p "$OUT"
 TAG=${TAG:-r01}
 WL=${WL:-c3 c4}
 for W in $WL; do
-  timeout -k 10 400 python -u bench.py --workload $W --steps ${STEPS:-3} --warmup 1 ${BENCH_ARGS:-} \
+  timeout -k 10 400 python -u bench.py --full --workload $W --steps ${STEPS:-3} --warmup 1 ${BENCH_ARGS:-} \
     > "$OUT/bench_${W}_$TAG.log" 2>&1
   st=$?; tail -2 "$OUT/bench_${W}_$TAG.log"
   if [ $st -ne 0 ]; then echo "STOP after bench $W (exit $st)"; exit $st; fi
