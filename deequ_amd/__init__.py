@@ -9,7 +9,7 @@ from .analyzers import (Analyzer, ApproxCountDistinct, Completeness, Compliance,
                         DataTypeInstances,
                         Distinctness, Entropy, FrequencyBasedAnalyzer, GroupingAnalyzer, Histogram,
                         Correlation, MaxLength, Maximum, Mean, MinLength, Minimum, MutualInformation,
-                        Preconditions,
+                        PatternMatch, Preconditions,
                         ScanShareableAnalyzer, ScanShareableFrequencyBasedAnalyzer, Size,
                         StandardDeviation, StandardScanShareableAnalyzer, Sum, Uniqueness,
                         UniqueValueRatio)

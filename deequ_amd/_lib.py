@@ -23,7 +23,7 @@ DQ_COL_DEVICE = 0x1
 
 (DQ_OP_SIZE, DQ_OP_COMPLETENESS, DQ_OP_COMPLIANCE, DQ_OP_SUM, DQ_OP_MEAN, DQ_OP_STDDEV,
  DQ_OP_MINIMUM, DQ_OP_MAXIMUM, DQ_OP_APPROX_COUNT_DISTINCT, DQ_OP_DATATYPE, DQ_OP_MIN_LENGTH,
- DQ_OP_MAX_LENGTH, DQ_OP_CORRELATION) = range(1, 14)
+ DQ_OP_MAX_LENGTH, DQ_OP_CORRELATION, DQ_OP_PATTERN_MATCH) = range(1, 15)
 
 DQ_P_COLUMN, DQ_P_LIT_INT, DQ_P_LIT_FLOAT, DQ_P_LIT_NULL, DQ_P_COALESCE, DQ_P_LIT_STRING = 1, 2, 3, 4, 5, 6
 DQ_P_CAST_DOUBLE = 7
@@ -121,6 +121,8 @@ DIAG_SIGNATURES = {
     "dq_diag_key_pack": (c_int, [c_char_p, c_int32, POINTER(c_uint64), c_char_p, POINTER(c_int32), POINTER(c_int32)]),
     "dq_diag_uuid_pack": (c_int, [c_char_p, c_int32, POINTER(c_uint64), c_char_p, POINTER(c_int32)]),
     "dq_diag_eval_predicate": (c_int, [POINTER(DqPredicate), POINTER(DqColumn), c_int, c_int64, c_void_p]),
+    "dq_diag_regex_match": (c_int, [c_char_p, c_int32, c_char_p, c_int64, POINTER(c_int32), POINTER(c_int32),
+                                    POINTER(c_int32)]),
 }
 
 

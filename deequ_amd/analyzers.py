@@ -350,6 +350,28 @@ class MaxLength(StandardScanShareableAnalyzer):
 
 
 @dataclass(frozen=True)
+class PatternMatch(StandardScanShareableAnalyzer):
+    """The fraction of rows whose value holds a non-empty match of `pattern`, a java.util.regex
+    pattern as text (the reference's `pattern.toString`), PatternMatch.scala:37-55; state
+    NumMatchesAndCount.  A pattern outside the subset the GPU answers exactly raises
+    UnsupportedOnGpu when the plan is built -- the JVM caller runs it on Spark."""
+    column: str
+    pattern: str
+    where: Optional[str] = None
+    name = "PatternMatch"
+    DQ_KIND = L.DQ_OP_PATTERN_MATCH
+
+    def instance(self):
+        return self.column
+
+    # (no additionalPreconditions: the reference declares none -- an unknown column fails the
+    # aggregation itself, and so the analyzer, when its op is built)
+
+    def __str__(self):
+        return "PatternMatch(%s,%s,%s)" % (self.column, self.pattern, _opt(self.where))
+
+
+@dataclass(frozen=True)
 class Correlation(StandardScanShareableAnalyzer):
     """Pearson correlation of two numeric columns (Correlation.scala:65-105); state
     CorrelationState, metric ck / sqrt(xMk * yMk)."""

@@ -25,6 +25,7 @@
 #include "dq_uuidpack.h"
 #include "dq_numparse.h"
 #include "dq_predeval.h"
+#include "dq_regex.h"
 #include "../../include/deequ_amd_diag.h"
 #include "hll_p9_tables.h"
 
@@ -720,7 +721,7 @@ static bool fast_variant(ScanTask* t, int* variant) {
 }
 
 // ------------------------------------------------------------------------------ plan
-enum Target { TGT_HOST_SIZE = 0, TGT_SCAN = 1, TGT_HLL = 2, TGT_DTYPE = 3, TGT_STRLEN = 4, TGT_CORR = 5 };
+enum Target { TGT_HOST_SIZE = 0, TGT_SCAN = 1, TGT_HLL = 2, TGT_DTYPE = 3, TGT_STRLEN = 4, TGT_CORR = 5, TGT_REGEX = 6 };
 
 struct OpSlot {
   int kind;
@@ -791,12 +792,18 @@ struct dq_plan : Stager {
   std::vector<HllTask> hll_launch, dtype_launch;
   std::vector<HllTask> len_tasks;    // MinLength / MaxLength: {column, type, where}
   std::vector<CorrTask> corr_tasks;  // Correlation: {x, y, where}
+  // PatternMatch: {column, where, DFA}; the distinct patterns' images back to back in d_rx_dfas
+  std::vector<RegexTask> regex_tasks;
+  std::vector<std::string> regex_patterns;
+  std::vector<uint32_t> regex_offsets;  // of each pattern's image in regex_images
+  std::vector<uint8_t> regex_images;
+  uint32_t regex_lds = 0;  // bytes of the largest staged image (byte map + table)
   std::vector<Program> programs;  // generic predicate programs -> batch masks
   // device state
   std::vector<dq_status> op_status;  // per op, after dq_plan_finish
   bool pred_cast = false;  // a predicate program casts a string to double (its own kernel: the parser's scratch)
   DevBuf d_tasks, d_groups, d_ranges, d_hll, d_progs, d_insns, d_pool, d_acc, d_partials, d_regs,
-      d_cols, d_masks, d_mask_words, d_dtype, d_dtype_counts, d_len, d_len_out, d_corr, d_corr_part, d_corr_acc, d_str;
+      d_cols, d_masks, d_mask_words, d_dtype, d_dtype_counts, d_len, d_len_out, d_corr, d_corr_part, d_corr_acc, d_str, d_rx, d_rx_dfas, d_rx_out;
   int64_t mask_words = 0;
   // pinned descriptor staging (DevColumn + DevMask arrays) guarded by an event
   void* h_desc = nullptr;
@@ -839,7 +846,8 @@ struct dq_plan : Stager {
   }
 };
 
-static dq_status check_op(const dq_op& op, const int32_t* types, int n_cols) {
+// dfa (optional): receives a PatternMatch op's compiled pattern, so that plan creation compiles it once.
+static dq_status check_op(const dq_op& op, const int32_t* types, int n_cols, regex::Dfa* dfa = nullptr) {
   auto need_col = [&](bool numeric) -> dq_status {
     if (op.column < 0 || op.column >= n_cols) return fail(DQ_ERR_INVALID, "op column out of range");
     if (!valid_type(types[op.column])) return fail(DQ_ERR_INVALID, "invalid column type");
@@ -863,6 +871,19 @@ static dq_status check_op(const dq_op& op, const int32_t* types, int n_cols) {
       if (types[op.column] != DQ_T_UTF8)
         return fail(DQ_ERR_UNSUPPORTED, "analyzer needs a string column (Preconditions.isString)");
       break;
+    case DQ_OP_PATTERN_MATCH: {
+      DQ_TRY(need_col(false));
+      if (types[op.column] != DQ_T_UTF8)  // (Spark would cast the column to string; this path does not)
+        return fail(DQ_ERR_UNSUPPORTED, "PatternMatch needs a string column on the GPU path");
+      if (op.predicate.n_insns != 0 || op.predicate.strings_len < 0 ||
+          (op.predicate.strings_len > 0 && !op.predicate.strings))
+        return fail(DQ_ERR_INVALID, "PatternMatch: the pattern travels as predicate.strings with n_insns = 0");
+      regex::Dfa local;
+      std::string err;
+      if (!regex::compile(op.predicate.strings, op.predicate.strings_len, dfa ? dfa : &local, &err))
+        return fail(DQ_ERR_UNSUPPORTED, err);
+      break;
+    }
     case DQ_OP_CORRELATION:
       DQ_TRY(need_col(true));
       if (op.column2 < 0 || op.column2 >= n_cols) return fail(DQ_ERR_INVALID, "op column2 out of range");
@@ -896,7 +917,8 @@ extern "C" dq_status dq_plan_create(dq_ctx* ctx, const dq_op* ops, int n_ops,
     return fail(DQ_ERR_INVALID, "NULL argument");
   for (int c = 0; c < n_columns; ++c)
     if (!valid_type(column_types[c])) return fail(DQ_ERR_INVALID, "invalid column type");
-  for (int i = 0; i < n_ops; ++i) DQ_TRY(check_op(ops[i], column_types, n_columns));
+  std::vector<regex::Dfa> op_dfas((size_t)std::max(0, n_ops));  // of the PatternMatch ops
+  for (int i = 0; i < n_ops; ++i) DQ_TRY(check_op(ops[i], column_types, n_columns, &op_dfas[i]));
 
   DQ_HIP(hipSetDevice(ctx->device));
   dq_plan* plan = new dq_plan();
@@ -1043,6 +1065,34 @@ extern "C" dq_status dq_plan_create(dq_ctx* ctx, const dq_op* ops, int n_ops,
         slot.task = t;
         break;
       }
+      case DQ_OP_PATTERN_MATCH: {
+        plan->col_used[op.column] = true;
+        slot.target = TGT_REGEX;
+        const std::string pat(reinterpret_cast<const char*>(op.predicate.strings), (size_t)op.predicate.strings_len);
+        int d = -1;  // one image per distinct pattern
+        for (size_t k = 0; k < plan->regex_patterns.size(); ++k)
+          if (plan->regex_patterns[k] == pat) d = (int)k;
+        if (d < 0) {
+          const std::vector<uint8_t> img = op_dfas[i].image();
+          d = (int)plan->regex_patterns.size();
+          plan->regex_patterns.push_back(pat);
+          plan->regex_offsets.push_back((uint32_t)plan->regex_images.size());
+          plan->regex_images.insert(plan->regex_images.end(), img.begin(), img.end());
+          plan->regex_lds = std::max(plan->regex_lds, (uint32_t)img.size() - regex::kRegexHeaderBytes);
+        }
+        const uint32_t off = plan->regex_offsets[d];
+        int t = -1;
+        for (size_t k = 0; k < plan->regex_tasks.size(); ++k)
+          if (plan->regex_tasks[k].column == op.column && plan->regex_tasks[k].where_mask == where_prog &&
+              plan->regex_tasks[k].dfa_off == off)
+            t = (int)k;
+        if (t < 0) {
+          plan->regex_tasks.push_back(RegexTask{op.column, where_prog, off, 0});
+          t = (int)plan->regex_tasks.size() - 1;
+        }
+        slot.task = t;
+        break;
+      }
       case DQ_OP_CORRELATION: {
         plan->col_used[op.column] = true;
         plan->col_used[op.column2] = true;
@@ -1155,6 +1205,9 @@ extern "C" dq_status dq_plan_create(dq_ctx* ctx, const dq_op* ops, int n_ops,
       (s = plan->d_len_out.ensure(std::max<size_t>(1, plan->len_tasks.size()) * 3 * sizeof(uint64_t))) != DQ_OK ||
       (s = upload(plan->d_corr, plan->corr_tasks.data(), plan->corr_tasks.size() * sizeof(CorrTask))) != DQ_OK ||
       (s = plan->d_corr_acc.ensure(std::max<size_t>(1, plan->corr_tasks.size()) * sizeof(CorrAcc))) != DQ_OK ||
+      (s = upload(plan->d_rx, plan->regex_tasks.data(), plan->regex_tasks.size() * sizeof(RegexTask))) != DQ_OK ||
+      (s = upload(plan->d_rx_dfas, plan->regex_images.data(), plan->regex_images.size())) != DQ_OK ||
+      (s = plan->d_rx_out.ensure(std::max<size_t>(1, plan->regex_tasks.size()) * 2 * sizeof(uint64_t))) != DQ_OK ||
       (s = upload(plan->d_progs, progs.data(), progs.size() * sizeof(PredProgram))) != DQ_OK ||
       (s = upload(plan->d_insns, insns.data(), insns.size() * sizeof(PredInsn))) != DQ_OK ||
       (s = upload(plan->d_pool, pool.data(), pool.size())) != DQ_OK ||
@@ -1174,7 +1227,7 @@ extern "C" dq_status dq_plan_create(dq_ctx* ctx, const dq_op* ops, int n_ops,
   }
   if (e == hipSuccess) e = hipEventCreateWithFlags(&plan->desc_done, hipEventDisableTiming);
   const char* side_env = std::getenv("DQ_PLAN_SIDE");  // 0: the string pass on the plan's stream (A/B)
-  if (e == hipSuccess && !plan->str_tasks.empty() && !(side_env && side_env[0] == '0')) {
+  if (e == hipSuccess && (!plan->str_tasks.empty() || !plan->regex_tasks.empty()) && !(side_env && side_env[0] == '0')) {
     e = StreamPool::get().acquire(ctx->device, &plan->side_stream);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&plan->side_ready, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&plan->side_done, hipEventDisableTiming);
@@ -1242,6 +1295,8 @@ extern "C" dq_status dq_plan_reset(dq_plan* plan) {
     DQ_HIP(hipMemsetAsync(plan->d_dtype_counts.ptr, 0, plan->dtype_tasks.size() * 5 * sizeof(uint64_t), plan->stream));
   if (!plan->len_tasks.empty())
     DQ_HIP(hipMemsetAsync(plan->d_len_out.ptr, 0, plan->len_tasks.size() * 3 * sizeof(uint64_t), plan->stream));
+  if (!plan->regex_tasks.empty())
+    DQ_HIP(hipMemsetAsync(plan->d_rx_out.ptr, 0, plan->regex_tasks.size() * 2 * sizeof(uint64_t), plan->stream));
   if (!plan->corr_tasks.empty())  // all-zero CorrAcc = the empty state (n = 0)
     DQ_HIP(hipMemsetAsync(plan->d_corr_acc.ptr, 0, plan->corr_tasks.size() * sizeof(CorrAcc), plan->stream));
   DQ_HIP(hipStreamSynchronize(plan->stream));
@@ -1459,14 +1514,26 @@ extern "C" dq_status dq_plan_consume(dq_plan* plan, const dq_column* columns, in
                              plan->stream));
 
   const int n_str = (int)plan->str_tasks.size();
-  // the string pass first, on the side stream when there is other work to run beside it
-  const bool side = n_str > 0 && plan->side_stream && (n_scan > 0 || !plan->hll_launch.empty());
+  const int n_rx = (int)plan->regex_tasks.size();
+  // the string work (the fused string pass, PatternMatch) first, on the side stream when there is
+  // other work to run beside it
+  const bool beside_str = n_scan > 0 || !plan->hll_launch.empty();
+  const bool beside_rx = beside_str || !plan->dtype_launch.empty() || !plan->len_tasks.empty() || !plan->corr_tasks.empty();
+  const bool side = plan->side_stream && (n_str > 0 ? beside_str : (n_rx > 0 && beside_rx));
+  if (side) {
+    DQ_HIP(hipEventRecord(plan->side_ready, plan->stream));
+    DQ_HIP(hipStreamWaitEvent(plan->side_stream, plan->side_ready, 0));
+  }
+  if (n_rx > 0) {  // every PatternMatch of the plan in one launch
+    int64_t bpt = std::max<int64_t>(1, plan->target_blocks / n_rx);
+    bpt = std::min<int64_t>(bpt, (n_rows + kBlock - 1) / kBlock);
+    DQ_HIP(launch_regex(static_cast<const RegexTask*>(plan->d_rx.ptr), n_rx, d_cols, d_masks,
+                        static_cast<const uint8_t*>(plan->d_rx_dfas.ptr), plan->regex_lds, n_rows, (int)bpt,
+                        static_cast<unsigned long long*>(plan->d_rx_out.ptr), side ? plan->side_stream : plan->stream));
+    if (side && n_str == 0) DQ_HIP(hipEventRecord(plan->side_done, plan->side_stream));
+  }
   if (n_str > 0) {
     hipStream_t ss = side ? plan->side_stream : plan->stream;
-    if (side) {
-      DQ_HIP(hipEventRecord(plan->side_ready, plan->stream));
-      DQ_HIP(hipStreamWaitEvent(ss, plan->side_ready, 0));
-    }
     int64_t bpt = std::max<int64_t>(1, plan->target_blocks / n_str);
     bpt = std::min<int64_t>(bpt, chunks);
     DQ_HIP(launch_string_pass(static_cast<const StrTask*>(plan->d_str.ptr), n_str, d_cols, d_masks, n_rows, (int)bpt,
@@ -1560,6 +1627,7 @@ extern "C" dq_status dq_plan_finish(dq_plan* plan, dq_state* out, int n_out) {
   std::vector<uint64_t> dtc(plan->dtype_tasks.size() * 5);
   std::vector<uint64_t> lens(plan->len_tasks.size() * 3);
   std::vector<CorrAcc> corr(plan->corr_tasks.size());
+  std::vector<uint64_t> rx(plan->regex_tasks.size() * 2);
   // every result array comes back in ONE pass through a pinned bounce buffer (pageable copies
   // are staged by the runtime, tens of microseconds each), then one synchronize
   struct Back {
@@ -1568,6 +1636,7 @@ extern "C" dq_status dq_plan_finish(dq_plan* plan, dq_state* out, int n_out) {
     size_t bytes;
   };
   const Back backs[] = {{lens.data(), plan->d_len_out.ptr, lens.size() * sizeof(uint64_t)},
+                        {rx.data(), plan->d_rx_out.ptr, rx.size() * sizeof(uint64_t)},
                         {corr.data(), plan->d_corr_acc.ptr, corr.size() * sizeof(CorrAcc)},
                         {dtc.data(), plan->d_dtype_counts.ptr, dtc.size() * sizeof(uint64_t)},
                         {acc.data(), plan->d_acc.ptr, acc.size() * sizeof(ScanAcc)},
@@ -1618,6 +1687,12 @@ extern "C" dq_status dq_plan_finish(dq_plan* plan, dq_state* out, int n_out) {
       const uint64_t* l = &lens[(size_t)s.task * 3];
       o.has_value = l[0] > 0;
       o.value = s.kind == DQ_OP_MIN_LENGTH ? (double)(~l[1]) : (double)l[2];
+      continue;
+    }
+    if (s.target == TGT_REGEX) {  // the sum over zero selected rows is NULL (ifNoNullsIn, PatternMatch.scala:40-44)
+      o.has_value = rx[(size_t)s.task * 2] > 0;
+      o.count = (int64_t)rx[(size_t)s.task * 2];
+      o.num_matches = (int64_t)rx[(size_t)s.task * 2 + 1];
       continue;
     }
     if (s.target == TGT_CORR) {  // Correlation.fromAggregationResult: None unless n > 0 (:85-96)
@@ -1849,7 +1924,7 @@ extern "C" dq_status dq_state_merge(const dq_state* a, const dq_state* b, dq_sta
     case DQ_OP_SIZE:  // NumMatches.sum (Size.scala:25-27)
       r.num_matches = (int64_t)((uint64_t)a->num_matches + (uint64_t)b->num_matches);
       break;
-    case DQ_OP_COMPLETENESS: case DQ_OP_COMPLIANCE:  // NumMatchesAndCount.sum (Analyzer.scala:233-235)
+    case DQ_OP_COMPLETENESS: case DQ_OP_COMPLIANCE: case DQ_OP_PATTERN_MATCH:  // NumMatchesAndCount.sum (Analyzer.scala:233-235)
       r.num_matches = (int64_t)((uint64_t)a->num_matches + (uint64_t)b->num_matches);
       r.count = (int64_t)((uint64_t)a->count + (uint64_t)b->count);
       break;
@@ -1902,7 +1977,7 @@ extern "C" dq_status dq_state_metric(const dq_state* s, double* out) {
   if (!s->has_value) return fail(DQ_ERR_STATE, "empty state (all input values were NULL)");
   switch (s->kind) {
     case DQ_OP_SIZE: *out = (double)s->num_matches; break;
-    case DQ_OP_COMPLETENESS: case DQ_OP_COMPLIANCE:
+    case DQ_OP_COMPLETENESS: case DQ_OP_COMPLIANCE: case DQ_OP_PATTERN_MATCH:
       *out = s->count == 0 ? std::numeric_limits<double>::quiet_NaN() : (double)s->num_matches / (double)s->count;
       break;
     case DQ_OP_SUM: *out = s->sum; break;
@@ -1931,6 +2006,25 @@ extern "C" dq_status dq_diag_parse_double(const uint8_t* s, int64_t n, double* o
   double v = 0.0;
   *ok = numparse::parse_double(HostBytes{s}, (int32_t)n, &v);
   *out = v;
+  return DQ_OK;
+}
+
+// Host build of PatternMatch's regex engine (dq_regex.h): the compiler check_op runs, and the walker
+// dq_regex_kernel runs.
+extern "C" dq_status dq_diag_regex_match(const uint8_t* pattern, int32_t pattern_len, const uint8_t* text, int64_t n,
+                                         int32_t* matched, int32_t* n_states, int32_t* n_classes) {
+  if ((!pattern && pattern_len > 0) || pattern_len < 0 || (!text && n > 0) || n < 0 || !matched)
+    return fail(DQ_ERR_INVALID, "bad argument");
+  regex::Dfa dfa;
+  std::string err;
+  if (!regex::compile(pattern, pattern_len, &dfa, &err)) return fail(DQ_ERR_UNSUPPORTED, err);
+  struct Text {
+    const uint8_t* p;
+    uint32_t operator[](int64_t i) const { return p[i]; }
+  };
+  *matched = regex::regex_walk(dfa.cmap, dfa.table.data(), dfa.n_cols, dfa.start_row, Text{text}, n) ? 1 : 0;
+  if (n_states) *n_states = (int32_t)dfa.n_states;
+  if (n_classes) *n_classes = (int32_t)dfa.n_cols;
   return DQ_OK;
 }
 

@@ -128,6 +128,15 @@ struct StrTask {
   int32_t dt_index;
 };
 
+// PatternMatch task (dq_regex.hip): one compiled pattern (its image at dfas + dfa_off, dq_regex.h)
+// over one (column, where); two u64 per task {rows in scope, rows that match}.
+struct RegexTask {
+  int32_t column;
+  int32_t where_mask;  // -1 = none
+  uint32_t dfa_off;
+  int32_t pad;
+};
+
 // Correlation task (dq_pair.hip) and its running state CorrelationState(n, xAvg, yAvg, ck, xMk, yMk).
 struct CorrTask {
   int32_t x, y;
@@ -497,6 +506,10 @@ hipError_t launch_datatype(const HllTask* d_tasks, int n_tasks, const DevColumn*
 // {selected rows, max of ~length, max of length}.
 hipError_t launch_strlen(const HllTask* d_tasks, int n_tasks, const DevColumn* d_cols, const DevMask* d_masks,
                          int64_t n_rows, int blocks_per_task, unsigned long long* d_out, hipStream_t stream);
+// PatternMatch (dq_regex.hip): lds_bytes = the largest staged image (byte map + table) of the launch.
+hipError_t launch_regex(const RegexTask* d_tasks, int n_tasks, const DevColumn* d_cols, const DevMask* d_masks,
+                        const uint8_t* d_dfas, uint32_t lds_bytes, int64_t n_rows, int blocks_per_task,
+                        unsigned long long* d_out, hipStream_t stream);
 // Correlation (dq_pair.hip): per-block partials (n_tasks x blocks_per_task), then merged into d_acc.
 hipError_t launch_corr(const CorrTask* d_tasks, int n_tasks, const DevColumn* d_cols, const DevMask* d_masks,
                        int64_t n_rows, int blocks_per_task, CorrAcc* d_partials, CorrAcc* d_acc,

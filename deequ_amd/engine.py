@@ -46,7 +46,8 @@ def _pred_array(pred):
 
 def _fill_pred(dst: L.DqPredicate, packed) -> None:
     arr, pool, n_pool = packed
-    dst.code = arr
+    if len(arr):
+        dst.code = arr
     dst.n_insns = len(arr)
     if pool is not None:
         dst.strings = ctypes.cast(pool, ctypes.c_void_p)
@@ -56,12 +57,18 @@ def _fill_pred(dst: L.DqPredicate, packed) -> None:
 class OpSpec:
     """One dq_op: kind, column index, compiled predicate / where programs."""
 
-    def __init__(self, kind: int, column: int = -1, predicate=None, where=None, column2: int = -1):
+    def __init__(self, kind: int, column: int = -1, predicate=None, where=None, column2: int = -1,
+                 pattern: Optional[str] = None):
         self.kind = kind
         self.column = column
         self.column2 = column2
         self.predicate = _pred_array(predicate)
         self.where = _pred_array(where)
+        self.pattern = None
+        if pattern is not None:  # PatternMatch: the pattern text is the string pool of a program with no instructions
+            self.pattern = pattern.encode("utf-8")
+            self.predicate = ((L.DqPredInsn * 0)(),
+                              ctypes.create_string_buffer(self.pattern, max(1, len(self.pattern))), len(self.pattern))
 
     def fill(self, op: L.DqOp) -> None:
         op.kind = self.kind
@@ -136,6 +143,8 @@ def op_spec_for(analyzer, schema: Dict[str, str]) -> OpSpec:
         return OpSpec(kind, -1, None, where)
     if kind == L.DQ_OP_COMPLIANCE:
         return OpSpec(kind, -1, compile_predicate(analyzer.predicate, idx), where)
+    if kind == L.DQ_OP_PATTERN_MATCH:
+        return OpSpec(kind, idx[analyzer.column][0], None, where, pattern=analyzer.pattern)
     if kind == L.DQ_OP_CORRELATION:
         return OpSpec(kind, idx[analyzer.firstColumn][0], None, where, idx[analyzer.secondColumn][0])
     return OpSpec(kind, idx[analyzer.column][0], None, where)
@@ -146,15 +155,16 @@ _SUPPORTED: Dict[tuple, bool] = {}
 
 def op_supported(spec: OpSpec, schema: Dict[str, str]) -> None:
     """Raises UnsupportedOnGpu / DeequAmdError if the op is not GPU-eligible.  The answer for an
-    op without predicate programs depends only on (kind, column types), so accepted ones are
-    remembered: a profiler run checks hundreds of such ops, again on every run."""
+    op without predicate programs depends only on (kind, column types) -- and, for PatternMatch, on
+    the pattern -- so accepted ones are remembered: a profiler run checks hundreds of such ops,
+    again on every run."""
     types = _schema_info(schema)[1]
     key = None
-    if spec.predicate is None and spec.where is None:
+    if (spec.predicate is None or spec.pattern is not None) and spec.where is None:
         n = len(schema)
         t1 = types[spec.column] if 0 <= spec.column < n else None
         t2 = types[spec.column2] if 0 <= spec.column2 < n else None
-        key = (spec.kind, spec.column, spec.column2, n, t1, t2)
+        key = (spec.kind, spec.column, spec.column2, n, t1, t2, spec.pattern)
         if key in _SUPPORTED:
             return
     op = L.DqOp()

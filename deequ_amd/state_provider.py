@@ -7,7 +7,8 @@ Layout per analyzer, `id` = MurmurHash3.stringHash(analyzer.toString, 42) as a d
 (StateProvider.scala:82-84), every number big-endian as java.io.DataOutputStream writes it:
 
   Size                              {prefix}-{id}.bin   long numMatches
-  Completeness, Compliance          {prefix}-{id}.bin   long numMatches, long count
+  Completeness, Compliance,
+  PatternMatch                      {prefix}-{id}.bin   long numMatches, long count
   Sum, Minimum, Maximum,
   MinLength, MaxLength              {prefix}-{id}.bin   double
   Mean                              {prefix}-{id}.bin   double sum, long count
@@ -33,7 +34,7 @@ import numpy as np
 
 from .analyzers import (ApproxCountDistinct, Completeness, Compliance, Correlation, DataType,
                         FrequencyBasedAnalyzer, Histogram, MaxLength, Maximum, Mean, MinLength, Minimum,
-                        Size, StandardDeviation, Sum)
+                        PatternMatch, Size, StandardDeviation, Sum)
 from .states import (ApproxCountDistinctState, CorrelationState, DataTypeHistogram, MaxState, MeanState,
                      MinState, NumMatches, NumMatchesAndCount, StandardDeviationState, SumState)
 
@@ -128,7 +129,7 @@ class HdfsStateProvider:
         path = self._path(ident)
         if isinstance(analyzer, Size):
             self._write(path, struct.pack(">q", state.numMatches))
-        elif isinstance(analyzer, (Completeness, Compliance)):
+        elif isinstance(analyzer, (Completeness, Compliance, PatternMatch)):
             self._write(path, struct.pack(">qq", state.numMatches, state.count))
         elif isinstance(analyzer, Sum):
             self._write(path, struct.pack(">d", state.sum_value))
@@ -203,7 +204,7 @@ class HdfsStateProvider:
         path = self._path(ident)
         if isinstance(analyzer, Size):
             return NumMatches(struct.unpack(">q", self._read(path))[0])
-        if isinstance(analyzer, (Completeness, Compliance)):
+        if isinstance(analyzer, (Completeness, Compliance, PatternMatch)):
             return NumMatchesAndCount(*struct.unpack(">qq", self._read(path)))
         if isinstance(analyzer, Sum):
             return SumState(struct.unpack(">d", self._read(path))[0])

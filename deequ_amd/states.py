@@ -356,6 +356,7 @@ _BY_KIND = {
     L.DQ_OP_MIN_LENGTH: MinState,  # MinLength's state is a MinState (MinLength.scala:26)
     L.DQ_OP_MAX_LENGTH: MaxState,
     L.DQ_OP_CORRELATION: CorrelationState,
+    L.DQ_OP_PATTERN_MATCH: NumMatchesAndCount,  # PatternMatch.scala:38
 }
 
 

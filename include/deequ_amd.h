@@ -85,7 +85,12 @@ typedef enum dq_op_kind {
   DQ_OP_DATATYPE = 10,             /* DataType(column, where)           DataType.scala:152-183  */
   DQ_OP_MIN_LENGTH = 11,           /* MinLength(column, where)          MinLength.scala:25-41   */
   DQ_OP_MAX_LENGTH = 12,           /* MaxLength(column, where)          MaxLength.scala:25-41   */
-  DQ_OP_CORRELATION = 13           /* Correlation(column, column2, where) Correlation.scala:77-105 */
+  DQ_OP_CORRELATION = 13,          /* Correlation(column, column2, where) Correlation.scala:77-105 */
+  DQ_OP_PATTERN_MATCH = 14         /* PatternMatch(column, pattern, where) PatternMatch.scala:37-55: a
+                                      utf8 column; the pattern text (pattern.toString, UTF-8) travels as
+                                      predicate.strings[0 .. strings_len) with predicate.n_insns = 0.  A
+                                      pattern outside the exact subset (PatternMatch) is
+                                      DQ_ERR_UNSUPPORTED at plan time                                   */
 } dq_op_kind;
 
 /*
@@ -161,7 +166,7 @@ typedef struct dq_op {
   int32_t column;            /* batch column index; ignored for SIZE/COMPLIANCE */
   int32_t column2;           /* CORRELATION: the second column (secondColumn)    */
   int32_t reserved;          /* 0                                                */
-  dq_predicate predicate;    /* COMPLIANCE only                                */
+  dq_predicate predicate;    /* COMPLIANCE; PATTERN_MATCH: the pattern text    */
   dq_predicate where;        /* optional filter (Analyzers.conditionalSelection) */
 } dq_op;
 
@@ -173,7 +178,8 @@ typedef struct dq_op {
  * (Spark returned SQL NULL, e.g. Mean over an all-NULL column).  Which fields are meaningful
  * depends on `kind`:
  *   SIZE                         NumMatches(num_matches)
- *   COMPLETENESS, COMPLIANCE     NumMatchesAndCount(num_matches, count)
+ *   COMPLETENESS, COMPLIANCE,
+ *   PATTERN_MATCH                NumMatchesAndCount(num_matches, count)
  *   SUM                          SumState(sum)
  *   MEAN                         MeanState(sum, count)
  *   STDDEV                       StandardDeviationState(n, avg, m2)
