@@ -8,6 +8,7 @@ no CPU fallback.
 from .analyzers import (Analyzer, ApproxCountDistinct, Completeness, Compliance, CountDistinct, DataType,
                         DataTypeInstances,
                         Distinctness, Entropy, FrequencyBasedAnalyzer, GroupingAnalyzer, Histogram,
+                        KLLParameters, KLLSketch,
                         Correlation, MaxLength, Maximum, Mean, MinLength, Minimum, MutualInformation,
                         PatternMatch, Preconditions,
                         ScanShareableAnalyzer, ScanShareableFrequencyBasedAnalyzer, Size,
@@ -15,7 +16,7 @@ from .analyzers import (Analyzer, ApproxCountDistinct, Completeness, Compliance,
                         UniqueValueRatio)
 from .frequencies import FrequenciesAndNumRows, FrequencyTable
 from .engine import Plan, current_device, run_scan, set_device
-from .metrics import (Distribution, DistributionValue, DoubleMetric, EmptyStateException, Entity,
+from .metrics import (BucketDistribution, BucketValue, KLLMetric, Distribution, DistributionValue, DoubleMetric, EmptyStateException, Entity,
                       Failure, HistogramMetric,
                       IllegalAnalyzerParameterException, MetricCalculationException,
                       MetricCalculationRuntimeException, NoSuchColumnException, Success,
@@ -24,8 +25,10 @@ from .runner import (Analysis, AnalysisRunBuilder, AnalysisRunner, AnalyzerConte
                      InMemoryStateProvider)
 from .states import (ApproxCountDistinctState, CorrelationState, DataTypeHistogram, MaxState, MeanState, MinState,
                      NumMatches,
-                     NumMatchesAndCount, StandardDeviationState, State, SumState)
+                     NumMatchesAndCount, StandardDeviationState, State, SumState,
+                     KLLState, NonSampleCompactor, QuantileNonSample)
 from .state_provider import HdfsStateProvider
+from . import kll
 from .arrow import ArrowBatch, ArrowTable
 from .table import Column, PartitionedTable, Table
 

@@ -92,6 +92,10 @@ class DqFreqGroup(Structure):
                 ("reserved", c_int32)]
 
 
+class DqKllColumn(Structure):
+    _fields_ = [("column", c_int32), ("sketch_size", c_int32), ("shrinking_factor", c_double)]
+
+
 class ArrowSchema(Structure):
     """struct ArrowSchema of the Arrow C Data Interface (include/deequ_amd.h)."""
 
@@ -123,6 +127,8 @@ DIAG_SIGNATURES = {
     "dq_diag_eval_predicate": (c_int, [POINTER(DqPredicate), POINTER(DqColumn), c_int, c_int64, c_void_p]),
     "dq_diag_regex_match": (c_int, [c_char_p, c_int32, c_char_p, c_int64, POINTER(c_int32), POINTER(c_int32),
                                     POINTER(c_int32)]),
+    "dq_diag_kll_sketch": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_double, c_int64, c_void_p, c_int64,
+                                   POINTER(c_int64)]),
 }
 
 
@@ -200,6 +206,13 @@ SIGNATURES = {
     "dq_group_freq_summary": (c_int, [c_void_p, c_void_p, c_int64, POINTER(DqFreqSummary)]),
     "dq_group_freq_top": (c_int, [c_void_p, c_void_p, c_int, POINTER(DqFreqGroup), c_int64, c_void_p, c_int64,
                                   POINTER(c_int64), POINTER(c_int64)]),
+    "dq_kll_supported": (c_int, [c_int32, c_double]),
+    "dq_kll_create": (c_int, [c_void_p, POINTER(DqKllColumn), c_int, POINTER(c_int32), c_int, c_int64,
+                              POINTER(c_void_p)]),
+    "dq_kll_consume": (c_int, [c_void_p, POINTER(DqColumn), c_int, c_int64]),
+    "dq_kll_finish": (c_int, [c_void_p, POINTER(c_int64), c_int]),
+    "dq_kll_export": (c_int, [c_void_p, c_int, c_void_p, c_int64, POINTER(c_int64)]),
+    "dq_kll_destroy": (c_int, [c_void_p]),
 }
 
 _lib = None

@@ -393,6 +393,93 @@ class Correlation(StandardScanShareableAnalyzer):
         return "Correlation(%s,%s,%s)" % (self.firstColumn, self.secondColumn, _opt(self.where))
 
 
+@dataclass(frozen=True)
+class KLLParameters:
+    """KLLParameters(sketchSize, shrinkingFactor, numberOfBuckets) (KLLSketch.scala:82)."""
+    sketchSize: int
+    shrinkingFactor: float
+    numberOfBuckets: int
+
+    def __str__(self):
+        from .javafmt import java_double_to_string
+        return "KLLParameters(%d,%s,%d)" % (self.sketchSize, java_double_to_string(float(self.shrinkingFactor)),
+                                            self.numberOfBuckets)
+
+
+@dataclass(frozen=True)
+class KLLSketch(Analyzer):
+    """KLLSketch(column, kllParameters) (KLLSketch.scala:90-176): a quantile sketch of a numeric
+    column; state KLLState, metric KLLMetric (a BucketDistribution).  In the reference it is a
+    ScanShareableAnalyzer that the runner takes out of the fused scan and hands to KLLRunner
+    (AnalysisRunner.scala:152-160, :193); here it is sketched by the dq_kll_* family (deequ_amd.kll),
+    all KLL analyzers of a run in one pass.  The sketch is deterministic; which rows meet in which
+    compaction is fixed by the slab / tree layout of DESIGN.md (KLLSketch)."""
+    column: str
+    kllParameters: Optional[KLLParameters] = None
+    name = "KLL"
+
+    DEFAULT_SKETCH_SIZE = 2048
+    DEFAULT_SHRINKING_FACTOR = 0.64
+    MAXIMUM_ALLOWED_DETAIL_BINS = 100
+
+    @property
+    def sketchSize(self) -> int:
+        return self.DEFAULT_SKETCH_SIZE if self.kllParameters is None else self.kllParameters.sketchSize
+
+    @property
+    def shrinkingFactor(self) -> float:
+        return self.DEFAULT_SHRINKING_FACTOR if self.kllParameters is None else self.kllParameters.shrinkingFactor
+
+    @property
+    def numberOfBuckets(self) -> int:
+        return self.MAXIMUM_ALLOWED_DETAIL_BINS if self.kllParameters is None else self.kllParameters.numberOfBuckets
+
+    def instance(self):
+        return self.column
+
+    def preconditions(self):
+        def param_check(_schema):  # PARAM_CHECK (:105-111)
+            if self.numberOfBuckets > self.MAXIMUM_ALLOWED_DETAIL_BINS:
+                raise IllegalAnalyzerParameterException(
+                    "Cannot return KLL Sketch related values for more than %d values"
+                    % self.MAXIMUM_ALLOWED_DETAIL_BINS)
+        return [param_check, Preconditions.hasColumn(self.column), Preconditions.isNumeric(self.column)]
+
+    def computeStateFrom(self, data):
+        from .kll import compute_kll_states
+        return compute_kll_states(data, [self])[self]
+
+    def computeMetricFrom(self, state):
+        """:125-160, the bucket arithmetic in the reference's evaluation order."""
+        from .metrics import BucketDistribution, BucketValue, KLLMetric, Success as _S
+        if state is None:
+            return KLLMetric(self.column, Failure(wrap_if_necessary(empty_state_exception(self))))
+        try:
+            sketch = state.qSketch
+            start, end = state.globalMin, state.globalMax
+            n = self.numberOfBuckets
+            buckets = []
+            for i in range(n):
+                lowBound = start + (end - start) * i / float(n)
+                highBound = start + (end - start) * (i + 1) / float(n)
+                if i == n - 1:
+                    count = sketch.getRank(highBound) - sketch.getRankExclusive(lowBound)
+                else:
+                    count = sketch.getRankExclusive(highBound) - sketch.getRankExclusive(lowBound)
+                buckets.append(BucketValue(lowBound, highBound, count))
+            parameters = [sketch.shrinkingFactor, float(sketch.sketchSize)]
+            return KLLMetric(self.column, _S(BucketDistribution(buckets, parameters, sketch.getCompactorItems())))
+        except Exception as e:  # noqa: BLE001 - the reference's Try { ... }
+            return KLLMetric(self.column, Failure(e))
+
+    def toFailureMetric(self, error):
+        from .metrics import KLLMetric
+        return KLLMetric(self.column, Failure(wrap_if_necessary(error)))
+
+    def __str__(self):
+        return "KLLSketch(%s,%s)" % (self.column, _opt(None if self.kllParameters is None else str(self.kllParameters)))
+
+
 class DataTypeInstances:
     """DataTypeInstances enumeration (DataType.scala:32-38): value ids and names."""
     Unknown, Fractional, Integral, Boolean, String = 0, 1, 2, 3, 4

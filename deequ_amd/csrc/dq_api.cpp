@@ -26,6 +26,7 @@
 #include "dq_numparse.h"
 #include "dq_predeval.h"
 #include "dq_regex.h"
+#include "dq_kll.h"
 #include "../../include/deequ_amd_diag.h"
 #include "hll_p9_tables.h"
 
@@ -2361,3 +2362,6 @@ extern "C" dq_status dq_profile_few_strings(dq_ctx* ctx, int32_t n, const dq_col
 
 // The analyzer list as the JVM serializes it.
 #include "dq_packed.inc"
+
+// KLLSketch's runner (dq_kll_*) over the host sketch of dq_kll.cpp and the kernels of dq_kll.hip.
+#include "dq_kll_api.inc"

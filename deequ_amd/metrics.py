@@ -184,3 +184,83 @@ class HistogramMetric:
             out.append(DoubleMetric(self.entity, "%s.ratio.%s" % (self.name, key), self.instance,
                                     Success(dv.ratio)))
         return out
+
+
+@dataclass(frozen=True)
+class BucketValue:
+    """BucketValue(lowValue, highValue, count) (metrics/KLLMetric.scala:24)."""
+    lowValue: float
+    highValue: float
+    count: int
+
+
+class BucketDistribution:
+    """BucketDistribution(buckets, parameters, data) (metrics/KLLMetric.scala:26-94):
+    parameters = [shrinkingFactor, sketchSize] (as KLLSketch.computeMetricFrom fills it,
+    KLLSketch.scala:148-149), data = the compactors' items level by level."""
+
+    def __init__(self, buckets, parameters, data):
+        self.buckets = list(buckets)
+        self.parameters = [float(p) for p in parameters]
+        self.data = [list(level) for level in data]
+
+    def computePercentiles(self):
+        """:31-40.  The reference reads parameters(0) as the sketch size and parameters(1) as the
+        shrinking factor -- the other way round from how they are stored; `reconstruct` only takes
+        the items from `data`, so the 99 quantiles do not depend on it.  Kept as it is."""
+        from .states import QuantileNonSample, _to_int
+        sketchSize = _to_int(self.parameters[0])
+        shrinkingFactor = self.parameters[1]
+        q = QuantileNonSample(sketchSize, shrinkingFactor)
+        q.reconstruct(sketchSize, shrinkingFactor, self.data)
+        return q.quantiles(100)
+
+    def __getitem__(self, key: int) -> BucketValue:  # apply(key)
+        return self.buckets[key]
+
+    def argmax(self) -> int:
+        """Index of the first bucket with the largest count (:55-65)."""
+        currentMax, maxBucket = 0, 0
+        for bucket in self.buckets:
+            if bucket.count > currentMax:
+                currentMax = bucket.count
+                maxBucket = self.buckets.index(bucket)
+        return maxBucket
+
+    def __eq__(self, that):
+        """:72-90: buckets, parameters and the data arrays element for element (`==` on doubles)."""
+        if not isinstance(that, BucketDistribution):
+            return False
+        if self.buckets != that.buckets or self.parameters != that.parameters or len(self.data) != len(that.data):
+            return False
+        return all(a == b for a, b in zip(self.data, that.data))
+
+    __hash__ = object.__hash__  # (the reference keeps the identity hash, :93)
+
+    def __repr__(self):
+        return "BucketDistribution(%r,%r,%r)" % (self.buckets, self.parameters, self.data)
+
+
+@dataclass(frozen=True)
+class KLLMetric:
+    """KLLMetric(column, value: Try[BucketDistribution]) (metrics/KLLMetric.scala:96-123)."""
+    column: str
+    value: Try
+
+    entity = Entity.Column
+    name = "KLL"
+
+    @property
+    def instance(self) -> str:
+        return self.column
+
+    def flatten(self):
+        if not self.value.isSuccess:
+            return [DoubleMetric(self.entity, "%s.buckets" % self.name, self.instance, self.value)]
+        dist = self.value.get()
+        out = [DoubleMetric(self.entity, "%s.buckets" % self.name, self.instance, Success(float(len(dist.buckets))))]
+        for b in dist.buckets:
+            out.append(DoubleMetric(self.entity, "%s.low" % self.name, self.instance, Success(b.lowValue)))
+            out.append(DoubleMetric(self.entity, "%s.high" % self.name, self.instance, Success(b.highValue)))
+            out.append(DoubleMetric(self.entity, "%s.count" % self.name, self.instance, Success(float(b.count))))
+        return out

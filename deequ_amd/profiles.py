@@ -8,8 +8,10 @@ Follows `src/main/scala/com/amazon/deequ/profiles/ColumnProfiler.scala` (profile
 * pass 2 (:147-173, :240-251): string columns typed Integral / Fractional are cast to
   LongType / DoubleType on the GPU (dq_cast_utf8, Spark 2.2.2 Cast semantics, :346-355,
   :427-445); then Minimum, Maximum, Mean, StandardDeviation and Sum of every numeric column in one
-  fused plan.  The reference's KLLSketch (a randomized sketch, :249) is out of scope, so `kll`
-  and `approxPercentiles` are None.
+  fused plan.  With `kllParameters` a KLLSketch of every numeric column (casted string columns
+  included) is the sixth analyzer (:249): it fills `kll` and `approxPercentiles` (:501-527).  The
+  reference sketches with its defaults when no parameters are given; here KLL is opt-in -- with
+  kllParameters=None both stay None and the profile is what it was (KLLSketch).
 * pass 3 (:175-205, :535-606): exact histograms of the low-cardinality columns with the GPU
   group-by (NULL -> "NullValue", values as Java toString), ratio = count / rows (:598-601).
 
@@ -94,9 +96,23 @@ class ColumnProfiles:
                     v = getattr(p, name)
                     if v is not None:
                         j[name] = v
+                if p.kll is not None:  # ColumnProfile.scala:125-152
+                    j["kll"] = OrderedDict([
+                        ("buckets", [OrderedDict([("low_value", b.lowValue), ("high_value", b.highValue),
+                                                  ("count", b.count)]) for b in p.kll.buckets]),
+                        ("sketch", OrderedDict([
+                            ("parameters", OrderedDict([("c", p.kll.parameters[0]), ("k", p.kll.parameters[1])])),
+                            # (Gson's rendering of double[][], kept as a string as the reference does)
+                            ("data", "[%s]" % ",".join("[%s]" % ",".join(_gson_double(v) for v in level)
+                                                      for level in p.kll.data))]))])
                 j["approxPercentiles"] = list(p.approxPercentiles or [])
             cols.append(j)
         return json.dumps({"columns": cols}, indent=2)
+
+
+def _gson_double(v: float) -> str:
+    from .javafmt import java_double_to_string
+    return java_double_to_string(float(v))
 
 
 @dataclass
@@ -311,6 +327,16 @@ class ColumnProfiler:
                 ctx2 = AnalysisRunner.onData(casted).addAnalyzers(second).run()
                 for k, v in _extract_numeric_statistics(ctx2).items():
                     numeric[k].update(v)
+            if kllParameters is not None:  # the sixth pass-2 analyzer (:249), sketched in one pass of its own
+                from .analyzers import KLLSketch
+                sketches = [KLLSketch(c, kllParameters) for c in relevant if generic.typeOf(c) in numeric_types]
+                if sketches:
+                    ctx_kll = AnalysisRunner.onData(casted).addAnalyzers(sketches).run()
+                    for a, m in ctx_kll.metricMap.items():  # successes only (:501-527)
+                        if m.value.isSuccess:
+                            dist = m.value.get()
+                            numeric.setdefault("kll", {})[a.column] = dist
+                            numeric.setdefault("approxPercentiles", {})[a.column] = sorted(dist.computePercentiles())
         except BaseException:
             if side:  # raised as the sequential run would, once the histogram pass has stopped:
                 # a running pass still launches GPU work, so it is awaited (its own error, if
@@ -663,9 +689,11 @@ def _create_profiles(columns, generic, numeric, histograms) -> ColumnProfiles:
                       histogram=histograms.get(name))
         if t in (DataTypeInstances.Integral, DataTypeInstances.Fractional):
             profiles[name] = NumericColumnProfile(
-                **common, kll=None, mean=numeric["mean"].get(name), maximum=numeric["maximum"].get(name),
+                **common, kll=numeric.get("kll", {}).get(name), mean=numeric["mean"].get(name),
+                maximum=numeric["maximum"].get(name),
                 minimum=numeric["minimum"].get(name), sum=numeric["sum"].get(name),
-                stdDev=numeric["stdDev"].get(name), approxPercentiles=None)
+                stdDev=numeric["stdDev"].get(name),
+                approxPercentiles=numeric.get("approxPercentiles", {}).get(name))
         else:
             profiles[name] = StandardColumnProfile(**common)
     return ColumnProfiles(profiles, generic.numRecords)

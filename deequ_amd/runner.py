@@ -142,12 +142,15 @@ class AnalysisRunner:
 
     @staticmethod
     def _runScanningAnalyzers(data, analyzers, aggregateWith, saveStatesWith) -> AnalyzerContext:
-        from .analyzers import GroupingAnalyzer
+        from .analyzers import GroupingAnalyzer, KLLSketch
         from .engine import op_spec_for, op_supported, run_scan_raw
         shareable = [a for a in analyzers if isinstance(a, ScanShareableAnalyzer)]
         grouping = [a for a in analyzers if isinstance(a, GroupingAnalyzer)]
-        others = [a for a in analyzers if not isinstance(a, (ScanShareableAnalyzer, GroupingAnalyzer))]
+        kll = [a for a in analyzers if isinstance(a, KLLSketch)]
+        others = [a for a in analyzers if not isinstance(a, (ScanShareableAnalyzer, GroupingAnalyzer, KLLSketch))]
         results = OrderedDict()
+        if kll:  # split off the shared scan and sketched together (AnalysisRunner.scala:152-160, :193)
+            results.update(AnalysisRunner._runKllAnalyzers(data, kll, aggregateWith, saveStatesWith).metricMap)
         # GPU eligibility is decided per analyzer at plan time (the reference's JNI shim
         # would leave an ineligible analyzer on Spark; here it becomes a failure metric)
         eligible = []
@@ -178,6 +181,33 @@ class AnalysisRunner:
                 results[a] = a.metricFromFrequencies(shared)
             else:
                 results[a] = a.calculate(data, aggregateWith, saveStatesWith)
+        return AnalyzerContext(results)
+
+    @staticmethod
+    def _runKllAnalyzers(data, analyzers, aggregateWith, saveStatesWith) -> AnalyzerContext:
+        """KLLRunner.computeKLLSketchesInExtraPass (KLLRunner.scala:89-122): one sketching pass for
+        every KLL analyzer, then calculateMetric per analyzer.  Parameters the GPU sketcher declines
+        fail their analyzer alone; an error of the pass fails them all."""
+        from .kll import check_parameters, compute_kll_states
+        results = OrderedDict()
+        usable = []
+        for a in analyzers:
+            try:
+                check_parameters(a.sketchSize, a.shrinkingFactor)
+                usable.append(a)
+            except Exception as e:  # noqa: BLE001
+                results[a] = a.toFailureMetric(e)
+        if usable:
+            try:
+                states = compute_kll_states(data, usable)
+                for a in usable:
+                    try:
+                        results[a] = a.calculateMetric(states[a], aggregateWith, saveStatesWith)
+                    except Exception as e:  # noqa: BLE001
+                        results[a] = a.toFailureMetric(e)
+            except Exception as e:  # noqa: BLE001
+                for a in usable:
+                    results[a] = a.toFailureMetric(e)
         return AnalyzerContext(results)
 
     @staticmethod

@@ -13,11 +13,15 @@ partial states do.
 * ApproxCountDistinctState -- ApproxCountDistinct.scala:26-40
 * DataTypeHistogram -- DataType.scala:40-52
 * CorrelationState -- Correlation.scala:26-57
+* KLLState, QuantileNonSample, NonSampleCompactor -- KLLSketch.scala:42-74, QuantileNonSample.scala,
+  NonSampleCompactor.scala (pure Python: the sketch is variable-size and has no POD image)
 """
 from __future__ import annotations
 
 import ctypes
-from typing import Optional, Sequence, Tuple
+import math
+import struct
+from typing import List, Optional, Sequence, Tuple
 
 from . import _lib as L
 
@@ -340,6 +344,331 @@ class CorrelationState(State):
 
     def __repr__(self):
         return "CorrelationState(%r,%r,%r,%r,%r,%r)" % self.fields()
+
+
+# ---------------------------------------------------------------- KLL sketches
+def _java_sort_key(x: float):
+    """Sort key with java.lang.Double.compare's order: -0.0 before 0.0, every NaN equal and last
+    (Python's stable sort then keeps NaNs in arrival order, as java.util.Arrays.sort of objects)."""
+    if x != x:
+        return (1, 0.0, 0.0)
+    return (0, x, math.copysign(1.0, x))
+
+
+def java_min(a: float, b: float) -> float:
+    """java.lang.Math.min(double, double): NaN if either is, -0.0 below 0.0."""
+    if a != a:
+        return a
+    if a == 0.0 and b == 0.0 and math.copysign(1.0, b) < 0:
+        return b
+    return a if a <= b else b
+
+
+def java_max(a: float, b: float) -> float:
+    if a != a:
+        return a
+    if a == 0.0 and b == 0.0 and math.copysign(1.0, a) < 0:
+        return b
+    return a if a >= b else b
+
+
+def _to_int(x: float) -> int:
+    """Scala's Double.toInt: NaN -> 0, saturating."""
+    if x != x:
+        return 0
+    if x >= 2147483647.0:
+        return 2147483647
+    if x <= -2147483648.0:
+        return -2147483648
+    return int(x)
+
+
+def _wrap_int(x: int) -> int:
+    x &= 0xFFFFFFFF
+    return x - (1 << 32) if x & 0x80000000 else x
+
+
+class NonSampleCompactor:
+    """NonSampleCompactor[Double] (NonSampleCompactor.scala:29-69).  The random offset of the
+    original KLL is commented out there (:49-51), so `compact` is deterministic."""
+
+    __slots__ = ("numOfCompress", "offset", "buffer")
+
+    def __init__(self):
+        self.numOfCompress = 0
+        self.offset = 0
+        self.buffer: List[float] = []
+
+    def compact(self) -> List[float]:
+        items = len(self.buffer)
+        n = items - (items % 2)
+        if self.numOfCompress % 2 == 1:
+            self.offset = 1 - self.offset
+        ordered = sorted(self.buffer[:n], key=_java_sort_key)
+        output = ordered[self.offset:n:2]
+        self.buffer = [self.buffer[items - 1]] if items % 2 == 1 else []  # the odd tail: the last appended item
+        self.numOfCompress += 1
+        return output
+
+
+class QuantileNonSample:
+    """QuantileNonSample[Double] (QuantileNonSample.scala:25-305): the reference's KLL sketch,
+    restated; the oracle the C++ host sketch (dq_kll.cpp) and the GPU kernels (dq_kll.hip) are
+    checked against level for level."""
+
+    def __init__(self, sketchSize: int, shrinkingFactor: float = 0.64):
+        self.sketchSize = int(sketchSize)
+        self.shrinkingFactor = float(shrinkingFactor)
+        self.curNumOfCompactors = 0
+        self.compactorActualSize = 0
+        self.compactorTotalSize = 0
+        self.compactors: List[NonSampleCompactor] = []
+        self.expand()
+
+    def reconstruct(self, sketchSize: int, shrinkingFactor: float, data) -> None:
+        self.sketchSize = int(sketchSize)
+        self.shrinkingFactor = float(shrinkingFactor)
+        self.compactors = [NonSampleCompactor() for _ in data]
+        for c, level in zip(self.compactors, data):
+            c.buffer = [float(v) for v in level]
+        self.curNumOfCompactors = len(self.compactors)
+        self.compactorActualSize = self.getCompactorItemsCount()
+        self.compactorTotalSize = self.getCompactorCapacityCount()
+
+    def getCompactorItems(self) -> List[List[float]]:
+        return [list(c.buffer) for c in self.compactors]
+
+    def expand(self) -> None:
+        self.compactors.append(NonSampleCompactor())
+        self.curNumOfCompactors = len(self.compactors)
+        self.compactorTotalSize = self.getCompactorCapacityCount()
+
+    def capacity(self, height: int) -> int:
+        """2 * (ceil(sketchSize * pow(shrinkingFactor, height) / 2).toInt + 1) (:78-80)."""
+        try:
+            p = math.pow(self.shrinkingFactor, height)
+        except (OverflowError, ValueError):
+            p = float("inf")
+        x = self.sketchSize * p / 2
+        c = _to_int(math.ceil(x) if x == x and abs(x) != float("inf") else x)
+        return _wrap_int(2 * _wrap_int(c + 1))
+
+    def update(self, item: float) -> None:
+        self.compactors[0].buffer.append(float(item))
+        self.compactorActualSize += 1
+        if self.compactorActualSize > self.compactorTotalSize:
+            self.condense()
+
+    def updateAll(self, items) -> None:
+        """`update` for every item in order, in bulk: the items up to the one that makes
+        actual > total are appended at once, then one condense -- what the GPU kernel does."""
+        items = [float(v) for v in items]
+        at = 0
+        while at < len(items):
+            room = self.compactorTotalSize - self.compactorActualSize
+            take = items[at:at + room + 1]
+            at += len(take)
+            self.compactors[0].buffer.extend(take)
+            self.compactorActualSize += len(take)
+            if self.compactorActualSize > self.compactorTotalSize:
+                self.condense()
+
+    def condense(self) -> None:
+        for height in range(len(self.compactors)):
+            if len(self.compactors[height].buffer) >= self.capacity(height):
+                if height + 1 >= self.curNumOfCompactors:
+                    self.expand()
+                self.compactors[height + 1].buffer.extend(self.compactors[height].compact())
+                self.compactorActualSize = self.getCompactorItemsCount()
+                break
+
+    def _output(self):
+        return [(v, 1 << i) for i, c in enumerate(self.compactors[:self.curNumOfCompactors]) for v in c.buffer]
+
+    def getRank(self, item: float) -> int:
+        """Weight of the items not greater than `item` (:163-171; Ordering.Double.gt is `>`)."""
+        return sum(w for v, w in self._output() if not v > item)
+
+    def getRankExclusive(self, item: float) -> int:
+        return sum(w for v, w in self._output() if v < item)
+
+    def merge(self, that: "QuantileNonSample") -> "QuantileNonSample":
+        """:215-230.  Mutates and returns self, as the reference does."""
+        while self.curNumOfCompactors < that.curNumOfCompactors:
+            self.expand()
+        for i in range(that.curNumOfCompactors):
+            self.compactors[i].buffer = self.compactors[i].buffer + that.compactors[i].buffer
+        self.compactorActualSize = self.getCompactorItemsCount()
+        while self.compactorActualSize >= self.compactorTotalSize:
+            before = (self.compactorActualSize, self.curNumOfCompactors)
+            self.condense()
+            if before == (self.compactorActualSize, self.curNumOfCompactors):
+                break  # (no level at its capacity: the reference would spin)
+        return self
+
+    def quantiles(self, q: int) -> List[float]:
+        """The quantiles 1/q .. (q-1)/q (:246-278)."""
+        output = self._output()
+        if not output:
+            return []
+        sortedItems = sorted(output, key=lambda iw: _java_sort_key(iw[0]))
+        totalWeight = sum(w for _, w in sortedItems)
+        nextThresh = totalWeight // q
+        curq, i, sumSoFar = 1, 0, 0
+        quantiles = [sortedItems[0][0]] * (q - 1)
+        while i < len(sortedItems) and curq < q:
+            while sumSoFar < nextThresh:
+                sumSoFar += sortedItems[i][1]
+                i += 1
+            quantiles[curq - 1] = sortedItems[min(i, len(sortedItems) - 1)][0]
+            curq += 1
+            nextThresh = curq * totalWeight // q
+        return quantiles
+
+    def getCompactorItemsCount(self) -> int:
+        return sum(len(c.buffer) for c in self.compactors[:self.curNumOfCompactors])
+
+    def getCompactorCapacityCount(self) -> int:
+        return sum(self.capacity(h) for h in range(self.curNumOfCompactors))
+
+    def copy(self) -> "QuantileNonSample":
+        out = QuantileNonSample.__new__(QuantileNonSample)
+        out.sketchSize, out.shrinkingFactor = self.sketchSize, self.shrinkingFactor
+        out.curNumOfCompactors = self.curNumOfCompactors
+        out.compactorActualSize, out.compactorTotalSize = self.compactorActualSize, self.compactorTotalSize
+        out.compactors = []
+        for c in self.compactors:
+            d = NonSampleCompactor()
+            d.numOfCompress, d.offset, d.buffer = c.numOfCompress, c.offset, list(c.buffer)
+            out.compactors.append(d)
+        return out
+
+    def weight(self) -> int:
+        """Sum of len(level i) * 2^i: the number of updates the sketch stands for."""
+        return sum(len(c.buffer) << i for i, c in enumerate(self.compactors))
+
+    def levels(self) -> List[tuple]:
+        """Per level (numOfCompress, offset, the items' bit patterns): what the parity tests compare."""
+        return [(c.numOfCompress, c.offset, struct.pack("<%dd" % len(c.buffer), *c.buffer)) for c in self.compactors]
+
+
+KLL_INIT_MIN = 2147483647.0   # Int.MaxValue.toDouble (KLLRunner.scala:28)
+KLL_INIT_MAX = -2147483648.0  # Int.MinValue.toDouble (KLLRunner.scala:29)
+
+
+class KLLState(State):
+    """KLLState(qSketch, globalMax, globalMin) (KLLSketch.scala:42-74)."""
+
+    def __init__(self, qSketch: QuantileNonSample, globalMax: float, globalMin: float):
+        self.qSketch = qSketch
+        self.globalMax = float(globalMax)
+        self.globalMin = float(globalMin)
+
+    def sum(self, other: "KLLState") -> "KLLState":
+        if not isinstance(other, KLLState):
+            raise TypeError("cannot sum KLLState with %s" % type(other).__name__)
+        # (the reference merges into this.qSketch in place; a copy keeps a persisted state intact)
+        merged = self.qSketch.copy().merge(other.qSketch)
+        return KLLState(merged, java_max(self.globalMax, other.globalMax), java_min(self.globalMin, other.globalMin))
+
+    __add__ = sum
+
+    def metricValue(self):
+        raise TypeError("KLLState is not a DoubleValuedState")
+
+    def to_dq(self):
+        raise TypeError("KLLState has no POD image: it travels through dq_kll_export")
+
+    def to_bytes(self) -> bytes:
+        """The UDAF's buffer (StatefulKLLSketch: min, max, then KLLSketchSerializer.serialize,
+        KLLSketchSerializer.scala:58-81), big-endian -- what KLLState.fromBytes reads."""
+        q = self.qSketch
+        out = [struct.pack(">dd", self.globalMin, self.globalMax),
+               struct.pack(">idiiii", q.sketchSize, q.shrinkingFactor, q.curNumOfCompactors, q.compactorActualSize,
+                           q.compactorTotalSize, len(q.compactors))]
+        for c in q.compactors:
+            out.append(struct.pack(">iii%dd" % len(c.buffer), c.numOfCompress, c.offset, len(c.buffer), *c.buffer))
+        return b"".join(out)
+
+    @classmethod
+    def from_bytes(cls, b: bytes) -> "KLLState":
+        """KLLState.fromBytes (KLLSketch.scala:64-72) over KLLSketchSerializer.deserialize (:83-115)."""
+        lo, hi = struct.unpack_from(">dd", b, 0)
+        k, c, cur, actual, total, n = struct.unpack_from(">idiiii", b, 16)
+        at = 16 + 28
+        q = QuantileNonSample(k, c)
+        q.compactors = []
+        for _ in range(n):
+            comp = NonSampleCompactor()
+            comp.numOfCompress, comp.offset, m = struct.unpack_from(">iii", b, at)
+            at += 12
+            comp.buffer = list(struct.unpack_from(">%dd" % m, b, at))
+            at += 8 * m
+            q.compactors.append(comp)
+        q.curNumOfCompactors, q.compactorActualSize, q.compactorTotalSize = cur, actual, total
+        return cls(q, hi, lo)
+
+    @classmethod
+    def from_export(cls, buf: bytes, sketchSize: int, shrinkingFactor: float) -> "KLLState":
+        """From the words of dq_kll_export / dq_diag_kll_sketch (include/deequ_amd.h)."""
+        (n,) = struct.unpack_from("<q", buf, 0)
+        lo, hi = struct.unpack_from("<dd", buf, 8)
+        heads = struct.unpack_from("<%dq" % (3 * n), buf, 24)
+        at = 24 + 24 * n
+        q = QuantileNonSample(sketchSize, shrinkingFactor)
+        q.compactors = []
+        for i in range(n):
+            comp = NonSampleCompactor()
+            m, comp.numOfCompress, comp.offset = heads[3 * i:3 * i + 3]
+            comp.buffer = list(struct.unpack_from("<%dd" % m, buf, at))
+            at += 8 * m
+            q.compactors.append(comp)
+        q.curNumOfCompactors = n
+        q.compactorActualSize = q.getCompactorItemsCount()
+        q.compactorTotalSize = q.getCompactorCapacityCount()
+        return cls(q, hi, lo)
+
+    def signature(self) -> tuple:
+        """Everything parity is pinned on, bit for bit: levels, numOfCompress, offset, min, max."""
+        return (tuple(self.qSketch.levels()), struct.pack("<dd", self.globalMin, self.globalMax))
+
+    def __eq__(self, o):
+        return isinstance(o, KLLState) and o.signature() == self.signature() and \
+            (o.qSketch.sketchSize, o.qSketch.shrinkingFactor) == (self.qSketch.sketchSize, self.qSketch.shrinkingFactor)
+
+    def __hash__(self):
+        return hash(self.signature())
+
+    def __repr__(self):
+        return "KLLState(levels=%s,max=%r,min=%r)" % ([len(c.buffer) for c in self.qSketch.compactors],
+                                                    self.globalMax, self.globalMin)
+
+
+DEFAULT_KLL_SLAB_ROWS = 1 << 16  # kDefaultSlabRows (deequ_amd/csrc/dq_kll.h)
+
+
+def kll_sketch_slabs(values, sketchSize: int, shrinkingFactor: float, slab_rows: int = DEFAULT_KLL_SLAB_ROWS) -> KLLState:
+    """The library's partitioning (KLLSketch) on the CPU mirror: `values` is one batch, a
+    sequence of floats with None for NULL; slabs of slab_rows rows each sketched as one reference
+    partition (KLLRunner.scala:150-177), merged by the balanced tree in slab order."""
+    values = list(values)
+    slabs = []
+    for r0 in range(0, max(len(values), 1), slab_rows):
+        q = QuantileNonSample(sketchSize, shrinkingFactor)
+        lo, hi = KLL_INIT_MIN, KLL_INIT_MAX
+        rows = [float(v) for v in values[r0:r0 + slab_rows] if v is not None]
+        for v in rows:
+            lo, hi = java_min(lo, v), java_max(hi, v)
+        q.updateAll(rows)
+        slabs.append([q, lo, hi])
+    step = 1
+    while step < len(slabs):
+        for j in range(0, len(slabs) - step, 2 * step):
+            a, b = slabs[j], slabs[j + step]
+            a[0].merge(b[0])
+            a[1], a[2] = java_min(a[1], b[1]), java_max(a[2], b[2])
+        step *= 2
+    return KLLState(slabs[0][0], slabs[0][2], slabs[0][1])
 
 
 _BY_KIND = {

@@ -599,6 +599,46 @@ dq_status dq_group_freq_summary(dq_group* g, dq_freq* owned, int64_t num_rows, d
 dq_status dq_group_freq_top(dq_group* g, dq_freq* owned, int n, dq_freq_group* groups, int64_t max_groups,
                             uint8_t* key_bytes, int64_t key_cap, int64_t* n_out, int64_t* key_bytes_out);
 
+/* ---------------------------------------------------------------- KLL sketches
+ * KLLSketch (KLLSketch.scala:90-170) has a runner of its own in the reference
+ * (KLLRunner.computeKLLSketchesInExtraPass, KLLRunner.scala:89-122) and a state of variable size
+ * (QuantileNonSample[Double] + globalMax / globalMin), so it has a small family here rather than a
+ * dq_op.  The reference's sketch is deterministic; its result depends only on the partitioning, which
+ * this library fixes (KLLSketch): a batch is cut into slabs of `slab_rows` consecutive
+ * rows, each slab is sketched as one reference partition (KLLRunner.scala:150-177), the slabs of a
+ * batch are merged by a balanced tree in slab order with QuantileNonSample.merge, and batches are
+ * merged in arrival order (KLLState.sum).  The result is a pure function of the rows, the parameters
+ * and slab_rows.
+ *
+ * Call sequence: dq_kll_create, dq_kll_consume per batch (synchronous), dq_kll_finish for the export
+ * sizes, dq_kll_export per sketched column, dq_kll_destroy.  Not thread-safe. */
+typedef struct dq_kll dq_kll;
+
+typedef struct dq_kll_column {
+  int32_t column;           /* batch column index: INT8..INT64, FLOAT32, FLOAT64          */
+  int32_t sketch_size;      /* KLLParameters.sketchSize (default 2048)                     */
+  double shrinking_factor;  /* KLLParameters.shrinkingFactor (default 0.64)                */
+} dq_kll_column;
+
+/* DQ_OK when the GPU sketcher takes these parameters.  DQ_ERR_UNSUPPORTED (dq_last_error names
+ * the bound) when the capacity of the sketch's levels exceeds what a workgroup's LDS holds, e.g.
+ * sketchSize 50000 or a shrinking factor >= 1: the caller sketches on Spark. */
+dq_status dq_kll_supported(int32_t sketch_size, double shrinking_factor);
+
+/* slab_rows = 0 selects the library's constant (65536 rows). */
+dq_status dq_kll_create(dq_ctx* ctx, const dq_kll_column* columns, int n, const int32_t* column_types,
+                        int n_columns, int64_t slab_rows, dq_kll** out);
+dq_status dq_kll_consume(dq_kll* k, const dq_column* columns, int n_columns, int64_t n_rows);
+/* sizes[i] = bytes dq_kll_export needs for sketched column i.  Without a consumed batch every
+ * sketch is empty (min = Int.MaxValue, max = Int.MinValue, KLLRunner.scala:28-29). */
+dq_status dq_kll_finish(dq_kll* k, int64_t* sizes, int n);
+/* Sketched column i as 8-byte little-endian words: int64 n_levels, double globalMin, double
+ * globalMax, per level {int64 length, int64 numOfCompress, int64 offset}, then the compactors'
+ * items (doubles) level by level.  *required = the bytes needed; DQ_ERR_SPACE when `capacity` is
+ * smaller (retry with a larger buffer). */
+dq_status dq_kll_export(dq_kll* k, int i, void* out, int64_t capacity, int64_t* required);
+dq_status dq_kll_destroy(dq_kll* k);
+
 #ifdef __cplusplus
 }
 #endif

@@ -81,6 +81,15 @@ dq_status dq_diag_uuid_pack(const uint8_t* key, int32_t len, uint64_t* words, ui
 dq_status dq_diag_regex_match(const uint8_t* pattern, int32_t pattern_len, const uint8_t* text, int64_t n,
                               int32_t* matched, int32_t* n_states, int32_t* n_classes);
 
+/* Host build of KLLSketch's whole layout (deequ_amd/csrc/dq_kll.cpp: the reference's sequential
+ * sketch; no GPU): values[r] is row r, NULL where valid[r] == 0 (valid may be NULL: no NULLs); the
+ * rows are cut into slabs of slab_rows, each sketched as one reference partition, and the slabs merged
+ * by the balanced tree dq_kll_consume uses.  The sketch is written as dq_kll_export writes it
+ * (same DQ_ERR_SPACE protocol).  slab_rows >= n gives the plain sequential sketch. */
+dq_status dq_diag_kll_sketch(const double* values, const uint8_t* valid, int64_t n, int32_t sketch_size,
+                             double shrinking_factor, int64_t slab_rows, void* out, int64_t capacity,
+                             int64_t* required);
+
 #ifdef __cplusplus
 }
 #endif
