@@ -21,7 +21,10 @@
  *   - Columns use the Arrow layout: validity bitmap LSB-first, 1 = valid (NULL pointer = no
  *     nulls), fixed-width values, utf8 = int32 offsets + bytes.  A column's buffers are either
  *     host memory (copied to HBM by the library) or device memory on the context's GPU
- *     (DQ_COL_DEVICE; used in place, never copied).
+ *     (DQ_COL_DEVICE; used in place, never copied).  Only rows [offset, offset + length) and
+ *     their validity bits are a column's content: what NULL slots hold (values, or the heap
+ *     bytes a NULL string spans), the bitmap's padding bits, and the rows, bits and heap bytes
+ *     outside the window are ignored (pinned by tests/test_gpu_hostile_*.py).
  *   - Plans are not thread-safe; use one plan per calling thread.  Contexts may be shared.
  */
 #ifndef DEEQU_AMD_H

@@ -204,6 +204,7 @@ def test_fast_equals_general_kernel(gpu, monkeypatch):
     an = _suite("i", ["i >= 0"]) + _suite("f", ["f > 5e5"])
     fast = d.run_scan(an, pt)
     monkeypatch.setenv("DQ_SCAN_FAST", "0")
+    monkeypatch.setenv("DEEQU_AMD_PLAN_CACHE", "0")  # (the pooled plan of `fast` keeps its kernels)
     general = d.run_scan(an, pt)
     monkeypatch.delenv("DQ_SCAN_FAST")
     for a in an:
