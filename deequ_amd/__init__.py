@@ -5,7 +5,7 @@ The public names mirror the reference's Scala API (`com.amazon.deequ.analyzers`,
 goes through the C-ABI library `libdeequ_amd.so` (hand-written gfx950 HIP kernels); there is
 no CPU fallback.
 """
-from .analyzers import (Analyzer, ApproxCountDistinct, Completeness, Compliance, CountDistinct, DataType,
+from .analyzers import (Analyzer, ApproxCountDistinct, ApproxQuantile, ApproxQuantiles, Completeness, Compliance, CountDistinct, DataType,
                         DataTypeInstances,
                         Distinctness, Entropy, FrequencyBasedAnalyzer, GroupingAnalyzer, Histogram,
                         KLLParameters, KLLSketch,
@@ -17,7 +17,7 @@ from .analyzers import (Analyzer, ApproxCountDistinct, Completeness, Compliance,
 from .frequencies import FrequenciesAndNumRows, FrequencyTable
 from .engine import Plan, current_device, run_scan, set_device
 from .metrics import (BucketDistribution, BucketValue, KLLMetric, Distribution, DistributionValue, DoubleMetric, EmptyStateException, Entity,
-                      Failure, HistogramMetric,
+                      Failure, HistogramMetric, KeyedDoubleMetric,
                       IllegalAnalyzerParameterException, MetricCalculationException,
                       MetricCalculationRuntimeException, NoSuchColumnException, Success,
                       WrongColumnTypeException)
@@ -26,9 +26,11 @@ from .runner import (Analysis, AnalysisRunBuilder, AnalysisRunner, AnalyzerConte
 from .states import (ApproxCountDistinctState, CorrelationState, DataTypeHistogram, MaxState, MeanState, MinState,
                      NumMatches,
                      NumMatchesAndCount, StandardDeviationState, State, SumState,
-                     KLLState, NonSampleCompactor, QuantileNonSample)
+                     KLLState, NonSampleCompactor, QuantileNonSample,
+                     ApproxQuantileState, PercentileDigest)
 from .state_provider import HdfsStateProvider
 from . import kll
+from . import quantiles
 from .arrow import ArrowBatch, ArrowTable
 from .table import Column, PartitionedTable, Table
 

@@ -96,6 +96,10 @@ class DqKllColumn(Structure):
     _fields_ = [("column", c_int32), ("sketch_size", c_int32), ("shrinking_factor", c_double)]
 
 
+class DqAqColumn(Structure):
+    _fields_ = [("column", c_int32), ("reserved", c_int32), ("relative_error", c_double)]
+
+
 class ArrowSchema(Structure):
     """struct ArrowSchema of the Arrow C Data Interface (include/deequ_amd.h)."""
 
@@ -213,6 +217,12 @@ SIGNATURES = {
     "dq_kll_finish": (c_int, [c_void_p, POINTER(c_int64), c_int]),
     "dq_kll_export": (c_int, [c_void_p, c_int, c_void_p, c_int64, POINTER(c_int64)]),
     "dq_kll_destroy": (c_int, [c_void_p]),
+    "dq_aq_supported": (c_int, [c_double]),
+    "dq_aq_create": (c_int, [c_void_p, POINTER(DqAqColumn), c_int, POINTER(c_int32), c_int, POINTER(c_void_p)]),
+    "dq_aq_consume": (c_int, [c_void_p, POINTER(DqColumn), c_int, c_int64]),
+    "dq_aq_finish": (c_int, [c_void_p, POINTER(c_int64), c_int]),
+    "dq_aq_export": (c_int, [c_void_p, c_int, c_void_p, c_int64, POINTER(c_int64)]),
+    "dq_aq_destroy": (c_int, [c_void_p]),
 }
 
 _lib = None

@@ -480,6 +480,114 @@ class KLLSketch(Analyzer):
         return "KLLSketch(%s,%s)" % (self.column, _opt(None if self.kllParameters is None else str(self.kllParameters)))
 
 
+def _check_quantile_parameters(quantiles, relativeError) -> None:
+    """PARAM_CHECKS (ApproxQuantile.scala:52-61, ApproxQuantiles.scala:42-53) with the messages of
+    MetricCalculationException.scala:59-67."""
+    from .javafmt import java_double_to_string
+    for quantile in quantiles:
+        if quantile < 0.0 or quantile > 1.0:
+            raise IllegalAnalyzerParameterException(
+                "Quantile parameter must be in the closed interval [0, 1]. Currently, the value is: %s!"
+                % java_double_to_string(float(quantile)))
+    if relativeError < 0.0 or relativeError > 1.0:
+        raise IllegalAnalyzerParameterException(
+            "Relative error parameter must be in the closed interval [0, 1]. Currently, the value is: %s!"
+            % java_double_to_string(float(relativeError)))
+
+
+@dataclass(frozen=True)
+class ApproxQuantile(Analyzer):
+    """ApproxQuantile(column, quantile, relativeError) (ApproxQuantile.scala:39-103): one quantile of
+    a numeric column from a Greenwald-Khanna digest; state ApproxQuantileState, a DoubleMetric named
+    ApproxQuantile-<quantile>.  In the reference it is a ScanShareableAnalyzer over Spark's
+    PercentileDigest UDAF; here the runner takes it out of the fused scan and the dq_aq_* family
+    (deequ_amd.quantiles) builds the digest, all quantile analyzers of a run in one pass.  The digest
+    is this project's own (ApproxQuantile): deterministic, every answer within
+    ceil(relativeError * n) ranks.  relativeError 0 and values below 0.001 raise UnsupportedOnGpu."""
+    column: str
+    quantile: float
+    relativeError: float = 0.01
+
+    @property
+    def name(self):
+        from .javafmt import java_double_to_string
+        return "ApproxQuantile-%s" % java_double_to_string(float(self.quantile))
+
+    def instance(self):
+        return self.column
+
+    def preconditions(self):
+        def param_checks(_schema):
+            _check_quantile_parameters([self.quantile], self.relativeError)
+        return [param_checks, Preconditions.hasColumn(self.column), Preconditions.isNumeric(self.column)]
+
+    def computeStateFrom(self, data):
+        from .quantiles import compute_quantile_states
+        return compute_quantile_states(data, [self])[self]
+
+    def calculateMetric(self, state, aggregateWith=None, saveStatesWith=None):
+        # fromAggregationResult (:67-84): a digest of no values (all NULL) is no state
+        if state is not None and not state.percentileDigest.getPercentiles([self.quantile]):
+            state = None
+        return super().calculateMetric(state, aggregateWith, saveStatesWith)
+
+    def computeMetricFrom(self, state):
+        if state is None:
+            return metric_from_failure(empty_state_exception(self), self.name, self.column, self.entity)
+        percentile = state.percentileDigest.getPercentiles([self.quantile])[0]
+        return metric_from_value(percentile, self.name, self.column, self.entity)
+
+    def __str__(self):
+        from .javafmt import java_double_to_string
+        return "ApproxQuantile(%s,%s,%s)" % (self.column, java_double_to_string(float(self.quantile)),
+                                             java_double_to_string(float(self.relativeError)))
+
+
+@dataclass(frozen=True)
+class ApproxQuantiles(Analyzer):
+    """ApproxQuantiles(column, quantiles, relativeError) (ApproxQuantiles.scala:38-107): several
+    quantiles from one digest; a KeyedDoubleMetric named ApproxQuantiles whose keys are
+    `quantile.toString`.  Unlike ApproxQuantile the state is kept when the column is all NULL."""
+    column: str
+    quantiles: tuple
+    relativeError: float = 0.01
+    name = "ApproxQuantiles"
+
+    def __post_init__(self):
+        object.__setattr__(self, "quantiles", tuple(float(q) for q in self.quantiles))
+
+    def instance(self):
+        return self.column
+
+    def preconditions(self):
+        def param_checks(_schema):
+            _check_quantile_parameters(self.quantiles, self.relativeError)
+        return [param_checks, Preconditions.hasColumn(self.column), Preconditions.isNumeric(self.column)]
+
+    def computeStateFrom(self, data):
+        from .quantiles import compute_quantile_states
+        return compute_quantile_states(data, [self])[self]
+
+    def computeMetricFrom(self, state):
+        from .javafmt import java_double_to_string
+        from .metrics import KeyedDoubleMetric, Success as _S
+        if state is None:
+            return self.toFailureMetric(empty_state_exception(self))
+        computed = state.percentileDigest.getPercentiles(list(self.quantiles))
+        results = {java_double_to_string(q): r for q, r in zip(self.quantiles, computed)}
+        return KeyedDoubleMetric(Entity.Column, "ApproxQuantiles", self.column, _S(results))
+
+    def toFailureMetric(self, error):
+        from .metrics import KeyedDoubleMetric
+        return KeyedDoubleMetric(Entity.Column, "ApproxQuantiles", self.column, Failure(wrap_if_necessary(error)))
+
+    def __str__(self):
+        from .javafmt import java_double_to_string
+        return "ApproxQuantiles(%s,List(%s),%s)" % (self.column,
+                                                    ", ".join(java_double_to_string(q) for q in self.quantiles),
+                                                    java_double_to_string(float(self.relativeError)))
+
+
 class DataTypeInstances:
     """DataTypeInstances enumeration (DataType.scala:32-38): value ids and names."""
     Unknown, Fractional, Integral, Boolean, String = 0, 1, 2, 3, 4

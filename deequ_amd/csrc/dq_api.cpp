@@ -27,6 +27,7 @@
 #include "dq_predeval.h"
 #include "dq_regex.h"
 #include "dq_kll.h"
+#include "dq_quantile.h"
 #include "../../include/deequ_amd_diag.h"
 #include "hll_p9_tables.h"
 
@@ -2365,3 +2366,6 @@ extern "C" dq_status dq_profile_few_strings(dq_ctx* ctx, int32_t n, const dq_col
 
 // KLLSketch's runner (dq_kll_*) over the host sketch of dq_kll.cpp and the kernels of dq_kll.hip.
 #include "dq_kll_api.inc"
+
+// ApproxQuantile's runner (dq_aq_*) over the host digest of dq_quantile.cpp and the kernels of dq_quantile.hip.
+#include "dq_quantile_api.inc"

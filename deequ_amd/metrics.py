@@ -122,6 +122,21 @@ class DoubleMetric:
         return [self]
 
 
+@dataclass(frozen=True)
+class KeyedDoubleMetric:
+    """KeyedDoubleMetric(entity, name, instance, value: Try[Map[String, Double]]) (Metric.scala:51-68)."""
+    entity: Entity
+    name: str
+    instance: str
+    value: Try
+
+    def flatten(self):
+        if self.value.isSuccess:
+            return [DoubleMetric(self.entity, "%s-%s" % (self.name, key), self.instance, Success(v))
+                    for key, v in self.value.get().items()]
+        return [DoubleMetric(self.entity, self.name, self.instance, Failure(self.value.exception))]
+
+
 def metric_from_value(value: float, name: str, instance: str, entity: Entity = Entity.Column):
     return DoubleMetric(entity, name, instance, Success(float(value)))
 

@@ -16,6 +16,8 @@ Layout per analyzer, `id` = MurmurHash3.stringHash(analyzer.toString, 42) as a d
   Correlation                       {prefix}-{id}.bin   double n, xAvg, yAvg, ck, xMk, yMk
   DataType                          {prefix}-{id}.bin   int 40, DataTypeHistogram.toBytes
   ApproxCountDistinct               {prefix}-{id}.bin   int 416, wordsToBytes (52 big-endian longs)
+  ApproxQuantile                    {prefix}-{id}.bin   int length, the digest's serialised form
+                                    (PercentileDigest.serialize; INTEGRATION.md: unverified against Spark)
   FrequencyBasedAnalyzer, Histogram {prefix}-{id}-frequencies.pqt (parquet: the grouping columns +
                                     com_amazon_deequ_dq_metrics_count) and
                                     {prefix}-{id}-num_rows.bin (long)
@@ -32,11 +34,11 @@ from typing import List
 
 import numpy as np
 
-from .analyzers import (ApproxCountDistinct, Completeness, Compliance, Correlation, DataType,
+from .analyzers import (ApproxCountDistinct, ApproxQuantile, Completeness, Compliance, Correlation, DataType,
                         FrequencyBasedAnalyzer, Histogram, MaxLength, Maximum, Mean, MinLength, Minimum,
                         PatternMatch, Size, StandardDeviation, Sum)
-from .states import (ApproxCountDistinctState, CorrelationState, DataTypeHistogram, MaxState, MeanState,
-                     MinState, NumMatches, NumMatchesAndCount, StandardDeviationState, SumState)
+from .states import (ApproxCountDistinctState, ApproxQuantileState, CorrelationState, DataTypeHistogram, MaxState, MeanState,
+                     MinState, NumMatches, NumMatchesAndCount, PercentileDigest, StandardDeviationState, SumState)
 
 COUNT_COL = "com_amazon_deequ_dq_metrics_count"  # Analyzer.scala:363-364
 # Histogram's state is `data.select(col.cast(string)).groupBy(column).count()`
@@ -151,6 +153,9 @@ class HdfsStateProvider:
             self._write(path, struct.pack(">6d", *state.fields()))
         elif isinstance(analyzer, StandardDeviation):
             self._write(path, struct.pack(">3d", state.n, state.avg, state.m2))
+        elif isinstance(analyzer, ApproxQuantile):  # (no case for ApproxQuantiles in the reference either)
+            b = state.percentileDigest.serialize()
+            self._write(path, struct.pack(">i", len(b)) + b)
         else:
             raise ValueError("Unable to persist state for analyzer %s." % analyzer)
 
@@ -224,6 +229,8 @@ class HdfsStateProvider:
             return CorrelationState(*struct.unpack(">6d", self._read(path)))
         if isinstance(analyzer, StandardDeviation):
             return StandardDeviationState(*struct.unpack(">3d", self._read(path)))
+        if isinstance(analyzer, ApproxQuantile):
+            return ApproxQuantileState(PercentileDigest.deserialize(self._load_bytes(path)))
         raise ValueError("Unable to load state for analyzer %s." % analyzer)
 
     def _load_bytes(self, path: str) -> bytes:

@@ -15,6 +15,8 @@ partial states do.
 * CorrelationState -- Correlation.scala:26-57
 * KLLState, QuantileNonSample, NonSampleCompactor -- KLLSketch.scala:42-74, QuantileNonSample.scala,
   NonSampleCompactor.scala (pure Python: the sketch is variable-size and has no POD image)
+* ApproxQuantileState, PercentileDigest -- ApproxQuantile.scala:29-37 over this project's
+  Greenwald-Khanna digest (ApproxQuantile; pure Python, the mirror of dq_quantile.cpp)
 """
 from __future__ import annotations
 
@@ -669,6 +671,165 @@ def kll_sketch_slabs(values, sketchSize: int, shrinkingFactor: float, slab_rows:
             a[1], a[2] = java_min(a[1], b[1]), java_max(a[2], b[2])
         step *= 2
     return KLLState(slabs[0][0], slabs[0][2], slabs[0][1])
+
+
+# ---------------------------------------------------------------- ApproxQuantile
+_CANONICAL_NAN = 0x7FF8000000000000
+DIGEST_COMPRESS_THRESHOLD = 10000  # written into the serialised form, not used here
+
+
+def double_sort_key(x: float) -> int:
+    """The 64-bit key whose unsigned order is java.lang.Double.compare's: -0.0 before 0.0, every NaN
+    (canonicalised first) last (ApproxQuantile)."""
+    (b,) = struct.unpack("<Q", struct.pack("<d", x))
+    if (b & 0x7FFFFFFFFFFFFFFF) > 0x7FF0000000000000:
+        b = _CANONICAL_NAN
+    return (~b & 0xFFFFFFFFFFFFFFFF) if b >> 63 else (b | (1 << 63))
+
+
+class PercentileDigest:
+    """The digest of ApproxQuantile(s): a Greenwald-Khanna summary, `sampled` = [(value, g, delta)] in
+    value order over `count` values, for `relativeError`.  The reference keeps Spark's
+    PercentileDigest, whose content depends on insertion order and partitioning; this one is
+    defined by DESIGN.md (ApproxQuantile): exact-rank batch summaries, merged in arrival order."""
+
+    def __init__(self, relativeError: float):
+        self.relativeError = float(relativeError)
+        self.count = 0
+        self.sampled: List[Tuple[float, int, int]] = []
+
+    @classmethod
+    def from_entries(cls, relativeError: float, count: int, entries) -> "PercentileDigest":
+        d = cls(relativeError)
+        d.count = int(count)
+        d.sampled = [(float(v), int(g), int(delta)) for v, g, delta in entries]
+        return d
+
+    def copy(self) -> "PercentileDigest":
+        return PercentileDigest.from_entries(self.relativeError, self.count, self.sampled)
+
+    def merge(self, that: "PercentileDigest") -> "PercentileDigest":
+        """In place, as the reference's digest.merge; `that` is left unchanged."""
+        if that.relativeError != self.relativeError:
+            raise ValueError("cannot merge digests of relativeError %r and %r" % (self.relativeError, that.relativeError))
+        if not that.sampled:
+            return self
+        if not self.sampled:
+            self.sampled, self.count = list(that.sampled), that.count
+            return self
+        a, b = self.sampled, that.sampled
+        merged, side = [], []
+        i = j = 0
+        while i < len(a) or j < len(b):  # by key; this side first on ties
+            take_a = j == len(b) or (i < len(a) and double_sort_key(a[i][0]) <= double_sort_key(b[j][0]))
+            if take_a:
+                merged.append(a[i])
+                i += 1
+            else:
+                merged.append(b[j])
+                j += 1
+            side.append(0 if take_a else 1)
+        nxt = [None, None]
+        grown = [0] * len(merged)
+        for k in range(len(merged) - 1, -1, -1):  # delta grows by g + delta - 1 of the other side's next entry
+            s = nxt[1 - side[k]]
+            grown[k] = merged[k][2] + (s[1] + s[2] - 1 if s is not None else 0)
+            nxt[side[k]] = merged[k]
+        merged = [(v, g, grown[k]) for k, (v, g, _) in enumerate(merged)]
+        self.count += that.count
+        threshold = int(math.floor(2.0 * self.relativeError * float(self.count)))
+        kept = []
+        head = merged[-1]
+        for k in range(len(merged) - 2, 0, -1):  # compress from the right; first and last stay
+            v, g, delta = merged[k]
+            if g + head[1] + head[2] <= threshold:
+                head = (head[0], head[1] + g, head[2])
+            else:
+                kept.append(head)
+                head = merged[k]
+        kept.append(head)
+        if len(merged) > 1:
+            kept.append(merged[0])
+        kept.reverse()
+        self.sampled = kept
+        return self
+
+    def getPercentiles(self, quantiles: Sequence[float]) -> List[float]:
+        """[] on an empty digest; else per q the entry that minimises max(t - rmin, rmax - t) for
+        t = ceil(q * count), the first on ties."""
+        if not self.sampled:
+            return []
+        out = []
+        for q in quantiles:
+            t = int(math.ceil(float(q) * float(self.count)))
+            rmin, best, at = 0, None, 0
+            for k, (_, g, delta) in enumerate(self.sampled):
+                rmin += g
+                err = max(t - rmin, rmin + delta - t)
+                if best is None or err < best:
+                    best, at = err, k
+            out.append(self.sampled[at][0])
+        return out
+
+    def serialize(self) -> bytes:
+        """Big-endian: int32 compressThreshold, float64 relativeError, int64 count, int32 len, then
+        float64 value, int32 g, int32 delta per entry (unverified against Spark)."""
+        out = [struct.pack(">idqi", DIGEST_COMPRESS_THRESHOLD, self.relativeError, self.count, len(self.sampled))]
+        for v, g, delta in self.sampled:
+            out.append(struct.pack(">dii", v, g, delta))
+        return b"".join(out)
+
+    @classmethod
+    def deserialize(cls, b: bytes) -> "PercentileDigest":
+        _, eps, count, n = struct.unpack_from(">idqi", b, 0)
+        entries = [struct.unpack_from(">dii", b, 24 + 16 * k) for k in range(n)]
+        return cls.from_entries(eps, count, entries)
+
+    def signature(self) -> tuple:
+        """Bit for bit: relativeError, count and every entry (values as their bits, so NaN and -0.0
+        compare as what they are)."""
+        return (struct.pack("<d", self.relativeError), self.count,
+                tuple((struct.pack("<d", v), g, delta) for v, g, delta in self.sampled))
+
+    def __eq__(self, o):
+        return isinstance(o, PercentileDigest) and o.signature() == self.signature()
+
+    def __hash__(self):
+        return hash(self.signature())
+
+    def __repr__(self):
+        return "PercentileDigest(relativeError=%r,count=%d,entries=%d)" % (self.relativeError, self.count,
+                                                                           len(self.sampled))
+
+
+class ApproxQuantileState(State):
+    """ApproxQuantileState(percentileDigest) (ApproxQuantile.scala:29-37)."""
+
+    def __init__(self, percentileDigest: PercentileDigest):
+        self.percentileDigest = percentileDigest
+
+    def sum(self, other: "ApproxQuantileState") -> "ApproxQuantileState":
+        if not isinstance(other, ApproxQuantileState):
+            raise TypeError("cannot sum ApproxQuantileState with %s" % type(other).__name__)
+        # (the reference merges into this.percentileDigest in place; a copy keeps a persisted state intact)
+        return ApproxQuantileState(self.percentileDigest.copy().merge(other.percentileDigest))
+
+    __add__ = sum
+
+    def metricValue(self):
+        raise TypeError("ApproxQuantileState is not a DoubleValuedState")
+
+    def to_dq(self):
+        raise TypeError("ApproxQuantileState has no POD image: it travels through dq_aq_export")
+
+    def __eq__(self, o):
+        return isinstance(o, ApproxQuantileState) and o.percentileDigest == self.percentileDigest
+
+    def __hash__(self):
+        return hash(self.percentileDigest)
+
+    def __repr__(self):
+        return "ApproxQuantileState(%r)" % self.percentileDigest
 
 
 _BY_KIND = {

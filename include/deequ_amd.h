@@ -642,6 +642,44 @@ dq_status dq_kll_finish(dq_kll* k, int64_t* sizes, int n);
 dq_status dq_kll_export(dq_kll* k, int i, void* out, int64_t capacity, int64_t* required);
 dq_status dq_kll_destroy(dq_kll* k);
 
+/* ---------------------------------------------------------------- approximate quantiles
+ * ApproxQuantile / ApproxQuantiles (ApproxQuantile.scala, ApproxQuantiles.scala) keep a
+ * Greenwald-Khanna digest of a numeric column cast to double, NULLs skipped, no `where`.  The
+ * reference's digest depends on Spark's partitioning; this library's is a pure function of the rows,
+ * relativeError and the batch boundaries (ApproxQuantile): every batch is summarised by
+ * the exact values at ranks 1, 1 + gap, ..., n with gap = max(1, floor(relativeError * n)), found on
+ * the GPU by a multi-rank radix select, and the batch summaries are merged on the host in arrival
+ * order.  One dq_aq serves every (column, relativeError) pair of a run: one launch per pass covers
+ * them all.
+ *
+ * Call sequence: dq_aq_create, dq_aq_consume per batch (synchronous), dq_aq_finish for the export
+ * sizes, dq_aq_export per digest, dq_aq_destroy.  Not thread-safe. */
+typedef struct dq_aq dq_aq;
+
+typedef struct dq_aq_column {
+  int32_t column;         /* a numeric column of the schema   */
+  int32_t reserved;
+  double relative_error;  /* relativeError (default 0.01)     */
+} dq_aq_column;
+
+/* DQ_OK when the GPU select serves this relativeError.  DQ_ERR_UNSUPPORTED, the message naming the
+ * bound, for 0 (an exact quantile needs a full sort) and for values below 0.001 (the select keeps at
+ * most 2048 target ranks per batch); DQ_ERR_INVALID outside [0, 1]. */
+dq_status dq_aq_supported(double relative_error);
+/* columns[i]: one digest; column_types[n_columns]: the dq_type of every column of the batches
+ * to come. */
+dq_status dq_aq_create(dq_ctx* ctx, const dq_aq_column* columns, int n, const int32_t* column_types, int n_columns,
+                       dq_aq** out);
+/* DQ_ERR_UNSUPPORTED for a batch of more than 2^31 - 1 rows (row counts and gaps are 32-bit). */
+dq_status dq_aq_consume(dq_aq* a, const dq_column* columns, int n_columns, int64_t n_rows);
+/* sizes[i] = bytes dq_aq_export needs for digest i.  Without a non-NULL value the digest is empty. */
+dq_status dq_aq_finish(dq_aq* a, int64_t* sizes, int n);
+/* Digest i in its serialised form, every field big-endian: int32 compressThreshold (10000), float64
+ * relativeError, int64 count, int32 len, then per entry float64 value, int32 g, int32 delta.
+ * *required = the bytes needed; DQ_ERR_SPACE when `capacity` is smaller. */
+dq_status dq_aq_export(dq_aq* a, int i, void* out, int64_t capacity, int64_t* required);
+dq_status dq_aq_destroy(dq_aq* a);
+
 #ifdef __cplusplus
 }
 #endif
