@@ -33,5 +33,6 @@ from . import kll
 from . import quantiles
 from .arrow import ArrowBatch, ArrowTable
 from .table import Column, PartitionedTable, Table
+from .schema import RowLevelSchema, RowLevelSchemaValidationResult, RowLevelSchemaValidator
 
 __all__ = [n for n in dir() if not n.startswith("_")]

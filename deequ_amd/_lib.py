@@ -100,6 +100,16 @@ class DqAqColumn(Structure):
     _fields_ = [("column", c_int32), ("reserved", c_int32), ("relative_error", c_double)]
 
 
+DQ_SCHEMA_STRING, DQ_SCHEMA_INT, DQ_SCHEMA_DECIMAL, DQ_SCHEMA_TIMESTAMP = range(4)
+DQ_SCHEMA_NOT_NULL, DQ_SCHEMA_HAS_MIN, DQ_SCHEMA_HAS_MAX, DQ_SCHEMA_HAS_PATTERN = 1, 2, 4, 8
+
+
+class DqSchemaDef(Structure):
+    _fields_ = [("kind", c_int32), ("column", c_int32), ("flags", c_int32), ("precision", c_int32),
+                ("scale", c_int32), ("pattern_len", c_int32), ("min_value", c_int64), ("max_value", c_int64),
+                ("pattern", c_char_p)]
+
+
 class ArrowSchema(Structure):
     """struct ArrowSchema of the Arrow C Data Interface (include/deequ_amd.h)."""
 
@@ -133,6 +143,8 @@ DIAG_SIGNATURES = {
                                     POINTER(c_int32)]),
     "dq_diag_kll_sketch": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_double, c_int64, c_void_p, c_int64,
                                    POINTER(c_int64)]),
+    "dq_diag_schema_cell": (c_int, [c_int32, c_char_p, c_int64, c_int32, c_int32, POINTER(c_int32),
+                                    POINTER(c_int64)]),
 }
 
 
@@ -223,6 +235,15 @@ SIGNATURES = {
     "dq_aq_finish": (c_int, [c_void_p, POINTER(c_int64), c_int]),
     "dq_aq_export": (c_int, [c_void_p, c_int, c_void_p, c_int64, POINTER(c_int64)]),
     "dq_aq_destroy": (c_int, [c_void_p]),
+    "dq_schema_create": (c_int, [c_void_p, POINTER(DqSchemaDef), c_int, POINTER(c_int32), c_int, POINTER(c_void_p)]),
+    "dq_schema_supported": (c_int, [POINTER(DqSchemaDef), c_int, POINTER(c_int32), c_int]),
+    "dq_schema_validate": (c_int, [c_void_p, POINTER(DqColumn), c_int, c_int64, POINTER(c_int64), POINTER(c_int64),
+                                   POINTER(c_int32)]),
+    "dq_schema_output_layout": (c_int, [c_void_p, c_int, c_int, POINTER(c_int32), POINTER(c_int64),
+                                        POINTER(c_int64), POINTER(c_int64)]),
+    "dq_schema_gather": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "dq_schema_selection": (c_int, [c_void_p, c_int, c_void_p, c_int64]),
+    "dq_schema_destroy": (c_int, [c_void_p]),
 }
 
 _lib = None

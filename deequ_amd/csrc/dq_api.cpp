@@ -28,6 +28,7 @@
 #include "dq_regex.h"
 #include "dq_kll.h"
 #include "dq_quantile.h"
+#include "dq_schema.h"
 #include "../../include/deequ_amd_diag.h"
 #include "hll_p9_tables.h"
 
@@ -2369,3 +2370,6 @@ extern "C" dq_status dq_profile_few_strings(dq_ctx* ctx, int32_t n, const dq_col
 
 // ApproxQuantile's runner (dq_aq_*) over the host digest of dq_quantile.cpp and the kernels of dq_quantile.hip.
 #include "dq_quantile_api.inc"
+
+// RowLevelSchemaValidator's runner (dq_schema_*) over the kernels of dq_schema.hip.
+#include "dq_schema_api.inc"

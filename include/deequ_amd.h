@@ -680,6 +680,66 @@ dq_status dq_aq_finish(dq_aq* a, int64_t* sizes, int n);
 dq_status dq_aq_export(dq_aq* a, int i, void* out, int64_t capacity, int64_t* required);
 dq_status dq_aq_destroy(dq_aq* a);
 
+/* ---------------------------------------------------------------- row-level schema validation
+ * RowLevelSchemaValidator.validate (schema/RowLevelSchemaValidator.scala:183-281) on batches of
+ * string-typed columns: per row the Kleene AND of the definitions' conjuncts; the TRUE rows are
+ * validRows (int definitions cast to int32, decimal definitions to int64 unscaled values, the last
+ * definition of a column deciding its cast), the FALSE rows invalidRows (as they came); a row whose
+ * conjunction is NULL (a NULL cell of an int definition with a minValue, line 246) is in neither.
+ *
+ * Call sequence per batch: dq_schema_validate (synchronous: counts and every output's layout are
+ * known when it returns), then per wanted output column dq_schema_output_layout and dq_schema_gather
+ * into device buffers the caller allocated -- the rows are written once, into memory their owner
+ * manages; nothing is left to release.  The input columns of a DQ_COL_DEVICE batch must stay alive
+ * until the last dq_schema_gather of that batch.  Outputs are in input row order, Arrow layout,
+ * offset 0.  Not thread-safe. */
+typedef struct dq_schema dq_schema;
+
+enum { DQ_SCHEMA_STRING = 0, DQ_SCHEMA_INT = 1, DQ_SCHEMA_DECIMAL = 2, DQ_SCHEMA_TIMESTAMP = 3 };
+#define DQ_SCHEMA_NOT_NULL 0x1    /* isNullable = false                                     */
+#define DQ_SCHEMA_HAS_MIN 0x2     /* min_value is set: minValue (int) / minLength (string)  */
+#define DQ_SCHEMA_HAS_MAX 0x4     /* max_value is set: maxValue (int) / maxLength (string)  */
+#define DQ_SCHEMA_HAS_PATTERN 0x8 /* pattern is set: matches (string)                       */
+
+typedef struct dq_schema_def {
+  int32_t kind;        /* DQ_SCHEMA_*                                          */
+  int32_t column;      /* index into column_types                              */
+  int32_t flags;       /* DQ_SCHEMA_NOT_NULL | HAS_MIN | HAS_MAX | HAS_PATTERN */
+  int32_t precision;   /* decimal                                              */
+  int32_t scale;
+  int32_t pattern_len;
+  int64_t min_value;   /* 32-bit range, as the reference's Option[Int]         */
+  int64_t max_value;
+  const uint8_t* pattern; /* UTF-8 text of the java.util.regex pattern         */
+} dq_schema_def;
+
+/* Compiles the definitions (patterns included, as PatternMatch's are).  DQ_ERR_UNSUPPORTED, with
+ * dq_last_error naming the definition: a timestamp definition, a pattern outside the exact regex
+ * subset (the compiler's message follows), a definition on a column that is not utf8, decimal
+ * precision above 18.  DQ_ERR_INVALID: precision outside 1..38, scale outside 0..precision, a
+ * column out of range, a bound outside 32 bits. */
+dq_status dq_schema_create(dq_ctx* ctx, const dq_schema_def* defs, int n_defs, const int32_t* column_types,
+                           int n_columns, dq_schema** out);
+/* The same checks without a device (the status and message dq_schema_create would give). */
+dq_status dq_schema_supported(const dq_schema_def* defs, int n_defs, const int32_t* column_types, int n_columns);
+/* Validates one batch.  def_flags (n_defs entries, may be NULL): 1 for a decimal definition that met
+ * a cell the GPU cannot judge exactly (a byte >= 0x80, an exponent beyond +-1000); the call then
+ * returns DQ_ERR_UNSUPPORTED and the batch has no outputs. */
+dq_status dq_schema_validate(dq_schema* s, const dq_column* columns, int n_columns, int64_t n_rows,
+                             int64_t* num_valid, int64_t* num_invalid, int32_t* def_flags);
+/* Output `which` (0 validRows, 1 invalidRows), column `column` of the last batch: its dq_type and
+ * the bytes of its three buffers (0 = the buffer is absent; bit buffers are whole 64-bit words;
+ * utf8 offsets always hold count + 1 entries). */
+dq_status dq_schema_output_layout(dq_schema* s, int which, int column, int32_t* type, int64_t* values_bytes,
+                                  int64_t* validity_bytes, int64_t* offsets_bytes);
+/* Writes that column into device buffers of those sizes (a buffer of 0 bytes may be NULL).
+ * Synchronous. */
+dq_status dq_schema_gather(dq_schema* s, int which, int column, void* values, void* validity, void* offsets);
+/* The source row of every output row, in row order, to host memory (DQ_ERR_SPACE when capacity,
+ * in entries, is below the output's row count). */
+dq_status dq_schema_selection(dq_schema* s, int which, int32_t* out, int64_t capacity);
+dq_status dq_schema_destroy(dq_schema* s);
+
 #ifdef __cplusplus
 }
 #endif

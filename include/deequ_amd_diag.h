@@ -90,6 +90,15 @@ dq_status dq_diag_kll_sketch(const double* values, const uint8_t* valid, int64_t
                              double shrinking_factor, int64_t slab_rows, void* out, int64_t capacity,
                              int64_t* required);
 
+/* Host build of RowLevelSchemaValidator's int and decimal cell tests (deequ_amd/csrc/dq_schema.h,
+ * the source dq_schema_eval_kernel runs on the device) on the non-NULL cell text[0 .. n).
+ * kind = DQ_SCHEMA_INT: UTF8String.toInt; kind = DQ_SCHEMA_DECIMAL: new java.math.BigDecimal(text)
+ * .setScale(scale, ROUND_HALF_UP) within `precision` (1..18) digits.  *result = 0 the cast is NULL
+ * (the cell is invalid), 1 it succeeds and *value = the int / the unscaled decimal, 2 (decimal
+ * only) the GPU declines the cell: a byte >= 0x80 or an exponent beyond +-1000. */
+dq_status dq_diag_schema_cell(int32_t kind, const uint8_t* text, int64_t n, int32_t precision, int32_t scale,
+                              int32_t* result, int64_t* value);
+
 #ifdef __cplusplus
 }
 #endif
