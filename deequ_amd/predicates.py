@@ -6,9 +6,15 @@ module plays that role for the subset deequ's Check DSL emits on numeric columns
 (Check.scala:594-943): comparisons, IN, BETWEEN, IS [NOT] NULL, COALESCE, AND/OR/NOT, with
 Spark 2.2.2's literal typing and coercion:
 
-* `3` is an integer literal, `3.5` a DECIMAL literal, `3.5e2` / `3.5D` a DOUBLE literal;
+* `3` is an integer literal, `3.5` a DECIMAL literal, `3.5e2` / `3.5D` a DOUBLE literal; an integer
+  literal beyond Long is a DECIMAL(p, 0) literal (AstBuilder.visitIntegerLiteral), and a sign
+  written before digits belongs to the literal (-9223372036854775808 is Long.MinValue);
 * long vs decimal compares exactly (DecimalPrecision); here that is rewritten into an exact
-  int64 comparison (x > 3.5  ==>  x >= 4;  x = 3.5  ==>  false-or-NULL);
+  int64 comparison (x > 3.5  ==>  x >= 4;  x = 3.5  ==>  false-or-NULL), and a bound outside
+  int64 decides it for every non-NULL value (x < 9223372036854775808  ==>  true-or-NULL): no
+  instruction carries an integer outside int64, `emit` refuses one;
+* IN casts the value and every element to ONE common type (InConversion: findWiderCommonType of
+  all of them), as COALESCE does its arguments (FunctionArgumentConversion), not pair by pair;
 * anything vs double / float column compares in fp64 with Spark's NaN-safe ordering;
 * float vs int / long compares in FloatType: the integral side is rounded to float (a literal on
   the host, a column per row through DQ_P_CAST to FLOAT32);
@@ -49,6 +55,17 @@ class UnsupportedPredicate(ValueError):
 
 class PredicateSyntaxError(ValueError):
     pass
+
+
+_INT64_MIN, _INT64_MAX = -(2 ** 63), 2 ** 63 - 1
+
+
+def _integer_literal(v: int):
+    """Spark 2.2 AstBuilder.visitIntegerLiteral: an integer literal that fits Int or Long is
+    integral, a larger one is a DECIMAL(p, 0) literal (compared exactly, never wrapped)."""
+    if _INT64_MIN <= v <= _INT64_MAX:
+        return ("lit", "int", v)
+    return ("lit", "dec", Fraction(v))
 
 
 # ----------------------------------------------------------------------------- lexer
@@ -212,10 +229,17 @@ class _Parser:
         t = self.take()
         kind, text = t
         if kind == "OP" and text in ("-", "+"):
+            if self.peek()[0] == "INT":
+                # the sign belongs to the literal (SqlBase.g4 `number: MINUS? INTEGER_VALUE`), so
+                # -9223372036854775808 is Long.MinValue, not the negation of a decimal
+                v = int(self.take()[1])
+                return _integer_literal(-v if text == "-" else v)
             inner = self._operand()
             if inner[0] != "lit" or inner[1] not in ("int", "dec", "dbl"):
                 raise UnsupportedPredicate("unary %s on a non-literal in %r" % (text, self.text))
             if text == "-":
+                if inner[1] == "int" and not _INT64_MIN <= -inner[2] <= _INT64_MAX:
+                    raise UnsupportedPredicate("negation overflows int64 in %r" % self.text)
                 return ("lit", inner[1], -inner[2])
             return inner
         if kind == "OP" and text == "(":
@@ -223,7 +247,7 @@ class _Parser:
             self.expect_op(")")
             return node
         if kind == "INT":
-            return ("lit", "int", int(text))
+            return _integer_literal(int(text))
         if kind == "DEC":
             return ("lit", "dec", Fraction(Decimal(text)))
         if kind == "DBL":
@@ -324,7 +348,23 @@ class _Compiler:
         return self.stype(node) == "f32"
 
     def emit(self, opcode, arg=0, i64=0, f64=0.0):
-        self.code.append((opcode, arg, int(i64), float(f64)))
+        i64 = int(i64)
+        if not _INT64_MIN <= i64 <= _INT64_MAX:  # the instruction's field would wrap modulo 2^64
+            raise UnsupportedPredicate("integer %d is outside int64" % i64)
+        self.code.append((opcode, arg, i64, float(f64)))
+
+    def widen_f32(self, node):
+        """After emit_value(node): Cast(FloatType -> DoubleType), exact, where Spark's common type
+        of a COALESCE or an IN list is DoubleType although `node` is FloatType.  The library takes
+        a FloatType value next to an integral one only through this explicit cast."""
+        if self.stype(node) == "f32":
+            self.emit(L.DQ_P_CAST, L.TYPE_CODES["float64"])
+
+    def emit_const_or_null(self, a, value: bool):
+        """TRUE / FALSE where the integral value `a` is not NULL, NULL where it is."""
+        self.emit_value(a, "int")
+        self.emit_value(a, "int")
+        self.emit(L.DQ_P_EQ if value else L.DQ_P_NE, L.DQ_CMP_AS_INT64)
 
     def emit_value(self, node, target: str):
         """Push `node`; target is the comparison's type class (int / dbl / str, or f32: Spark
@@ -380,8 +420,10 @@ class _Compiler:
             elif kind == "dec":
                 if target == "dbl":
                     self.emit(L.DQ_P_LIT_FLOAT, f64=float(v))
-                elif v.denominator == 1 and -(2 ** 63) <= v.numerator < 2 ** 63:
+                elif v.denominator == 1 and _INT64_MIN <= v.numerator <= _INT64_MAX:
                     self.emit(L.DQ_P_LIT_INT, i64=v.numerator)
+                elif v.denominator == 1:
+                    raise UnsupportedPredicate("decimal literal beyond int64 in an integer context")
                 else:
                     raise UnsupportedPredicate("non-integral decimal in an integer context")
             elif kind == "dbl":
@@ -394,12 +436,25 @@ class _Compiler:
                 raise UnsupportedPredicate("string literal in a numeric context")
         elif t == "coalesce":
             args = node[1]
-            if target == "dbl" and self.stype(node) == "f32":  # COALESCE typed FloatType
+            kinds = {self.stype(a) for a in args} - {"null"}
+            if "str" in kinds and len(kinds) > 1:
+                # Spark makes it StringType: the other arguments become their Java text, which the
+                # IR cannot produce (the library refuses the program for the same reason)
+                raise UnsupportedPredicate("COALESCE of a string with a non-string")
+            if "bool" in kinds and len(kinds) > 1:  # no common type: Spark fails the analysis
+                raise UnsupportedPredicate("COALESCE of mixed boolean/numeric")
+            own = self.stype(node)
+            if target == "dbl" and own == "f32":  # COALESCE typed FloatType
                 target = "f32"
-            self.emit_value(args[0], target)
-            for a in args[1:]:
-                self.emit_value(a, target)
-                self.emit(L.DQ_P_COALESCE)
+            for k, a in enumerate(args):
+                if kinds == {"bool"} and a[0] == "lit" and a[1] == "bool":
+                    self.emit(L.DQ_P_TRUE if a[2] else L.DQ_P_FALSE)  # a boolean, as its siblings are
+                else:
+                    self.emit_value(a, target)
+                    if own == "f64" and "int" in kinds:  # (float, integral, double | decimal)
+                        self.widen_f32(a)
+                if k:
+                    self.emit(L.DQ_P_COALESCE)
         else:
             raise UnsupportedPredicate("boolean expression used as a value")
 
@@ -464,25 +519,32 @@ class _Compiler:
             if b[0] != "lit":
                 raise UnsupportedPredicate("decimal-typed expression")
             d = b[2]
-            if d.denominator == 1:
+            if d.denominator == 1 and _INT64_MIN <= d.numerator <= _INT64_MAX:
                 self.emit_value(a, "int")
                 self.emit_value(b, "int")
                 self.emit(self._OPS[op], L.DQ_CMP_AS_INT64)
                 return
-            # exact long-vs-decimal comparison for a non-integral decimal d
+            # exact long-vs-decimal comparison for a decimal d that no int64 equals: non-integral,
+            # or (an integer literal beyond Long is a decimal) outside int64.  The order against
+            # every int64 is that of floor(d) / ceil(d); a bound outside int64 decides the
+            # comparison for every non-NULL value
             lo, hi = math.floor(d), math.ceil(d)
-            if op in ("<", "<="):
+            if op in ("<", "<="):  # a <= floor(d)
+                if lo > _INT64_MAX or lo < _INT64_MIN:
+                    self.emit_const_or_null(a, lo > _INT64_MAX)
+                    return
                 self.emit_value(a, "int")
                 self.emit(L.DQ_P_LIT_INT, i64=lo)
                 self.emit(L.DQ_P_LE, L.DQ_CMP_AS_INT64)
-            elif op in (">", ">="):
+            elif op in (">", ">="):  # a >= ceil(d)
+                if hi > _INT64_MAX or hi < _INT64_MIN:
+                    self.emit_const_or_null(a, hi < _INT64_MIN)
+                    return
                 self.emit_value(a, "int")
                 self.emit(L.DQ_P_LIT_INT, i64=hi)
                 self.emit(L.DQ_P_GE, L.DQ_CMP_AS_INT64)
             elif op in ("=", "!="):  # never equal: FALSE / TRUE, NULL when a is NULL
-                self.emit_value(a, "int")
-                self.emit_value(a, "int")
-                self.emit(L.DQ_P_NE if op == "=" else L.DQ_P_EQ, L.DQ_CMP_AS_INT64)
+                self.emit_const_or_null(a, op == "!=")
             else:  # <=> never matches and is never NULL
                 self.emit(L.DQ_P_FALSE)
             return
@@ -515,8 +577,24 @@ class _Compiler:
                 # Spark 2.2 InConversion widens a string/number IN list to StringType (string
                 # comparison of the numbers' text), not to double as a plain comparison does
                 raise UnsupportedPredicate("IN list mixing strings and numbers")
+            if "bool" in kinds and len(kinds) > 1:  # no common type: Spark fails the analysis
+                raise UnsupportedPredicate("IN list mixing booleans and numbers")
+            # Spark 2.2 InConversion casts the value and EVERY element to findWiderCommonType of all
+            # of them (the type a COALESCE of them would have), not pair by pair: a FloatType value
+            # IN (16777217, 3.5) compares in double, a long IN (float column, 16777216) in FloatType
+            common = self.stype(("coalesce", [x] + list(items)))
             for k, item in enumerate(items):
-                self.emit_cmp("=", x, item)
+                if common in ("f32", "f64") and self.vtype(item) != "null":
+                    target = "f32" if common == "f32" else "dbl"
+                    self.emit_value(x, target)
+                    if common == "f64":
+                        self.widen_f32(x)
+                    self.emit_value(item, target)
+                    if common == "f64":
+                        self.widen_f32(item)
+                    self.emit(L.DQ_P_EQ, L.DQ_CMP_AS_FLOAT64)
+                else:
+                    self.emit_cmp("=", x, item)
                 if k:
                     self.emit(L.DQ_P_OR)
         elif t == "truth":
@@ -525,7 +603,7 @@ class _Compiler:
                 self.emit(L.DQ_P_TRUE if v[2] else L.DQ_P_FALSE)
             elif v[0] == "col" and self.vtype(v) == "bool":
                 self.emit(L.DQ_P_COLUMN, self.column(v[1])[0])
-            elif v[0] == "cast" and v[2] == "bool":
+            elif (v[0] == "cast" and v[2] == "bool") or (v[0] == "coalesce" and self.stype(v) == "bool"):
                 self.emit_value(v, "int")
             elif v[0] in ("or", "and", "not", "cmp", "in", "isnull", "isnotnull", "truth"):
                 self.emit_bool(v)

@@ -554,7 +554,16 @@ class _Tok:
                         j += 1
                     while j < len(s) and s[j].isdigit():
                         j += 1
-                out.append(("num", s[i:j]))
+                num = s[i:j]
+                nxt = s[j + 1:j + 2]
+                if j < len(s) and s[j] in "dD" and not (nxt.isalnum() or nxt == "_"):
+                    out.append(("num", num, "D"))  # 0.1D: a DOUBLE literal (SqlBase.g4 DOUBLE_LITERAL)
+                    j += 1
+                elif j < len(s) and s[j] in "lL" and num.isdigit() and not nxt.isalnum():
+                    out.append(("num", num, "L"))  # 3L: a BIGINT literal
+                    j += 1
+                else:
+                    out.append(("num", num, ""))
                 i = j
             elif c.isalpha() or c == "_" or c == "`":
                 if c == "`":
@@ -715,9 +724,23 @@ def eval_predicate(text: str, table: OTable) -> List[Optional[bool]]:
     nrows = len(next(iter(table.values())).values)
     tk = _Tok(text)
 
+    def number(t, sign=""):
+        # Spark 2.2 AstBuilder: digits are an Int / Long literal when they fit, a DECIMAL(p, 0)
+        # beyond Long (visitIntegerLiteral); digits with a point a DECIMAL; an exponent or a D
+        # suffix a DOUBLE.  The sign is part of the literal (`number: MINUS? INTEGER_VALUE`), so
+        # -9223372036854775808 is Long.MinValue.
+        body = sign + t[1]
+        if "e" in t[1].lower() or t[2] == "D":
+            return ("lit", "double", body)
+        if t[1].isdigit() and -(1 << 63) <= int(body) < (1 << 63):
+            return ("lit", "int", body)
+        return ("lit", "decimal", body)
+
     def operand():
         t = tk.next()
         if t[0] == "op" and t[1] == "-":
+            if tk.peek()[0] == "num":
+                return number(tk.next(), "-")
             v = operand()
             return ("neg", v)
         if t[0] == "op" and t[1] == "(":
@@ -725,8 +748,7 @@ def eval_predicate(text: str, table: OTable) -> List[Optional[bool]]:
             assert tk.next() == ("op", ")")
             return ("paren", e)
         if t[0] == "num":
-            return ("lit", ("int" if all(ch.isdigit() for ch in t[1]) else
-                            ("double" if "e" in t[1].lower() else "decimal")), t[1])
+            return number(t)
         if t[0] == "str":  # adjacent literals concatenate (Spark 2.2 grammar: STRING+)
             v = t[1]
             while tk.peek()[0] == "str":
@@ -806,7 +828,23 @@ def eval_predicate(text: str, table: OTable) -> List[Optional[bool]]:
     tree = or_expr()
     assert tk.peek() == (None, None), "trailing tokens in %r" % text
 
+    # The type and getter of a node do not depend on the row: resolved once per node (the memo
+    # keeps the node, so an id is never answered for another object).
+    memo = {}
+
     def typed(node):
+        e = memo.get(id(node))
+        if e is None or e[0] is not node:
+            e = memo[id(node)] = (node, _typed(node))
+        return e[1]
+
+    def coerced_pair(a, b):
+        e = memo.get((id(a), id(b)))
+        if e is None or e[0] is not a or e[1] is not b:
+            e = memo[(id(a), id(b))] = (a, b, _coerced_pair(a, b))
+        return e[2]
+
+    def _typed(node):
         """Returns (kind, getter) where kind in int/decimal/double/string/bool."""
         if node[0] == "lit":
             kind, v = node[1], node[2]
@@ -823,7 +861,13 @@ def eval_predicate(text: str, table: OTable) -> List[Optional[bool]]:
                 return "bool", lambda r, x=v: x
             return "null", lambda r: None
         if node[0] == "col":
-            col = table[node[1]]
+            # spark.sql.caseSensitive=false (the 2.2 default): names resolve ignoring case
+            hits = [k for k in table if k.lower() == node[1].lower()]
+            if node[1] in table and len(hits) == 1:
+                hits = [node[1]]
+            if len(hits) != 1:
+                raise KeyError(node[1])
+            col = table[hits[0]]
             # FloatType keeps its own kind: Spark 2.2 compares float vs int/long as FloatType
             kind = ("int" if col.dtype in _INTEGRAL else "float" if col.dtype == "float32"
                     else "double" if col.dtype in _FRACTIONAL else col.dtype)
@@ -843,17 +887,33 @@ def eval_predicate(text: str, table: OTable) -> List[Optional[bool]]:
             kinds = [k for k, _ in parts if k != "null"]
             kind = _common(kinds)
 
+            # Spark 2.2 TypeCoercion.FunctionArgumentConversion: when the arguments differ in
+            # type, EVERY argument is Cast to findWiderCommonType of them before Coalesce picks
+            # one -- (int | long, float) is FloatType (numericPrecedence), so an integral
+            # argument is rounded to float whatever the COALESCE is later compared with; a string
+            # among them makes it StringType (stringPromotion) and the others their Java text.
             def get(r):
-                for _, g in parts:
+                for k, g in parts:
                     v = g(r)
-                    if v is not None:
-                        return v
+                    if v is None:
+                        continue
+                    if kind == "string" and k != "string":
+                        if k not in ("int", "float", "double", "bool"):
+                            raise ValueError("COALESCE of a string with a %s is outside the restated subset" % k)
+                        return java_double_to_string(v, single=True) if k == "float" else _java_to_string(v)
+                    if kind in ("float", "double", "decimal") and k != kind:
+                        return conv(v, k, kind)
+                    return v
                 return None
             return kind, get
         return "bool", lambda r, n=node: ev(n, r)
 
     def _common(kinds):
-        # Spark 2.2 TypeCoercion: float vs int/long -> FloatType; decimal vs float/double -> double
+        # Spark 2.2 TypeCoercion: float vs int/long -> FloatType; decimal vs float/double -> double;
+        # a string with anything atomic -> StringType (findWiderTypeForTwo's stringPromotion, for
+        # COALESCE arguments; comparisons take PromoteStrings in coerced_pair instead)
+        if "string" in kinds:
+            return "string"
         if "double" in kinds:
             return "double"
         if "float" in kinds:
@@ -882,7 +942,7 @@ def eval_predicate(text: str, table: OTable) -> List[Optional[bool]]:
             return str(v)
         return v
 
-    def coerced_pair(a, b):
+    def _coerced_pair(a, b):
         ka, ga = typed(a)
         kb, gb = typed(b)
         if ka == kb:
@@ -909,40 +969,58 @@ def eval_predicate(text: str, table: OTable) -> List[Optional[bool]]:
             return x >= y
         raise ValueError(op)
 
+    def compare(op, x, ka, y, kb, target):
+        """`x op y` after both sides are Cast to `target`; the casts come first, so a string
+        that does not parse is a NULL operand like any other."""
+        if target == "double_from_string":  # Cast(-> DoubleType): Java parseDouble
+            x = java_parse_double(x) if isinstance(x, str) else (None if x is None else float(x))
+            y = java_parse_double(y) if isinstance(y, str) else (None if y is None else float(y))
+        else:
+            x, y = conv(x, ka, target), conv(y, kb, target)
+        if x is None or y is None:
+            # EqualNullSafe is never NULL (nullable = false): TRUE when both operands are NULL
+            return (x is None and y is None) if op == "<=>" else None
+        if isinstance(x, float) and isinstance(y, float) and (x != x or y != y):
+            # Spark double comparison: NaN = NaN is true and NaN is the largest value
+            xn, yn = x != x, y != y
+            if op in ("=", "==", "<=>"):
+                return xn and yn
+            if op in ("!=", "<>"):
+                return not (xn and yn)
+            order = (1 if xn else 0) - (1 if yn else 0)
+            return {"<": order < 0, "<=": order <= 0, ">": order > 0, ">=": order >= 0}[op]
+        return cmp_values(op, x, y)
+
     def ev(node, r):
         t = node[0]
         if t == "cmp":
-            op = node[1]
             ka, ga, kb, gb, target = coerced_pair(node[2], node[3])
-            x, y = ga(r), gb(r)
-            if op == "<=>":
-                if x is None or y is None:
-                    return x is None and y is None
-            if x is None or y is None:
-                return None
-            if target == "double_from_string":  # Cast(-> DoubleType): Java parseDouble
-                x = java_parse_double(x) if isinstance(x, str) else float(x)
-                y = java_parse_double(y) if isinstance(y, str) else float(y)
-                if x is None or y is None:
-                    return None
-            else:
-                x, y = conv(x, ka, target), conv(y, kb, target)
-            if isinstance(x, float) and isinstance(y, float) and (x != x or y != y):
-                # Spark double comparison: NaN = NaN is true and NaN is the largest value
-                xn, yn = x != x, y != y
-                if op in ("=", "==", "<=>"):
-                    return xn and yn
-                if op in ("!=", "<>"):
-                    return not (xn and yn)
-                order = (1 if xn else 0) - (1 if yn else 0)
-                return {"<": order < 0, "<=": order <= 0, ">": order > 0, ">=": order >= 0}[op]
-            return cmp_values(op, x, y)
+            if "null" in (ka, kb) and node[1] != "<=>":
+                return None  # the NULL literal: NULL whatever the other side is
+            return compare(node[1], ga(r), ka, gb(r), kb, target)
         if t == "in":
             kx, gx = typed(node[1])
+            parts = [typed(item) for item in node[2]]
+            if all(k == "null" for k, _ in parts):
+                return None  # IN (NULL): NULL whatever the value is
             x = gx(r)
             if x is None:
                 return None
-            kinds = {kx} | {typed(item)[0] for item in node[2]}
+            kinds = {kx} | {k for k, _ in parts}
+            numeric = kinds - {"null"}
+            if len(numeric) > 1 and numeric <= {"int", "float", "double", "decimal"}:
+                # Spark 2.2 InConversion: the value and EVERY list element are Cast to
+                # findWiderCommonType of all of them, not pair by pair: `g IN (16777217, 3.5)`
+                # on a FloatType g compares in double, `l IN (g, 16777216)` in FloatType
+                target = _common(sorted(numeric))
+                saw_null = False
+                for k, g in parts:
+                    res = compare("=", x, kx, g(r), k, target)
+                    if res is True:
+                        return True
+                    if res is None:
+                        saw_null = True
+                return None if saw_null else False
             if "string" in kinds and kinds - {"string", "null"}:
                 # Spark 2.2 InConversion: a string/number IN list compares as strings
                 xs = x if kx == "string" else _java_to_string(x)
@@ -956,7 +1034,8 @@ def eval_predicate(text: str, table: OTable) -> List[Optional[bool]]:
                 return None if saw_null else False
             saw_null = False
             for item in node[2]:
-                res = ev(("cmp", "=", node[1], item), r)
+                ka, _, kb, gb, target = coerced_pair(node[1], item)
+                res = compare("=", x, ka, gb(r), kb, target)
                 if res is True:
                     return True
                 if res is None:

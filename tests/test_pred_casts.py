@@ -43,6 +43,7 @@ FLOATS = [float(np.float32(x)) for x in (16777216.0, 16777218.0, 3.0, 4.0, -3.5,
                                           float("nan"), 0.1, 65539.0, 2 ** 24 + 4)] + [None]
 BOOLS = [True, False, None]
 INTS = [0, 3, 4, -3, 127, 128, -129, 2147483647, -2147483648, 100, 101, 16777217, 16777219, None]
+STRINGS = ["3", " 4 ", "x", None, "2.5"]
 
 
 def _table(n=96, seed=5):
@@ -50,7 +51,7 @@ def _table(n=96, seed=5):
     pick = lambda xs: [xs[int(k)] for k in rng.integers(0, len(xs), n)]  # noqa: E731
     data = {"l": ("int64", pick(LONGS)), "d": ("float64", pick(DOUBLES)), "g": ("float32", pick(FLOATS)),
             "i": ("int32", pick(INTS)), "b": ("bool", pick(BOOLS)),
-            "s": ("string", pick(["3", " 4 ", "x", None, "2.5"]))}
+            "s": ("string", pick(STRINGS))}
     # make every LONGS / DOUBLES value appear at least once
     data["l"][1][:len(LONGS)] = LONGS
     data["d"][1][:len(DOUBLES)] = DOUBLES
