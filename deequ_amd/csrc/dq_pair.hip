@@ -12,7 +12,12 @@
 //    dx, dy, dx^2, dy^2, dx*dy against a wave-uniform shift (no fp64 divide per row), converts to
 //    (n, xAvg, yAvg, ck, xMk, yMk) and lanes/waves/blocks are combined with CorrelationState.sum
 //    (Correlation.scala:37-52) in a fixed order, so results are bitwise reproducible.
+//    xMk = Σdx² - (Σdx)²/n (and ck, yMk alike) is only accurate while the shift lies near the data,
+//    so the shift is the first selected finite pair of the wave's rows however far in that is
+//    (never (0, 0) while the wave has one), and a wave whose sums still cancel (moments_cancel,
+//    dq_scan_common.h: the shift was an outlier) sums its rows again about its own mean.
 #include "dq_internal.h"
+#include "dq_scan_common.h"
 
 namespace dq {
 
@@ -43,6 +48,13 @@ __device__ inline uint64_t wave_max(uint64_t v) {
     v = o > v ? o : v;
   }
   return v;
+}
+
+// Σ over the wave in a fixed order, the same bits in every lane.
+__device__ inline double wave_all_sum(double v) {
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d, 64);
+  return __shfl(v, 0, 64);
 }
 
 __device__ inline double as_double(const DevColumn& c, int64_t row) {
@@ -137,10 +149,12 @@ __global__ __launch_bounds__(kBlock) void dq_corr_kernel(const CorrTask* __restr
     return (!X.validity || bit_at(X.validity, row)) && (!Y.validity || bit_at(Y.validity, row)) &&
            (!wt || word_bit(wt, row));
   };
-  // wave-uniform shift: the first selected pair with finite values among the wave's first rows
+  // wave-uniform shift: the first selected pair with finite values among the wave's own rows.
+  // The search goes on past an unselected (or non-finite) prefix until it finds one, so a wave
+  // that has any finite pair never sums about (0, 0).
   double sx = 0.0, sy = 0.0;
-  for (uint32_t probe = 0; probe < 4; ++probe) {
-    const int64_t row = r0 + (int64_t)(probe * (kBlock / 64) + wave) * 64 + lane;
+  for (int64_t base = r0 + (int64_t)wave * 64; base < r1; base += kBlock) {
+    const int64_t row = base + lane;
     bool ok = false;
     double x = 0.0, y = 0.0;
     if (row < r1 && selected(row)) {
@@ -156,16 +170,36 @@ __global__ __launch_bounds__(kBlock) void dq_corr_kernel(const CorrTask* __restr
       break;
     }
   }
-  double n = 0.0, s_x = 0.0, s_y = 0.0, s_xx = 0.0, s_yy = 0.0, s_xy = 0.0;
-  for (int64_t row = r0 + threadIdx.x; row < r1; row += kBlock) {
-    if (!selected(row)) continue;
-    const double dx = as_double(X, row) - sx, dy = as_double(Y, row) - sy;
-    n += 1.0;
-    s_x += dx;
-    s_y += dy;
-    s_xx += dx * dx;
-    s_yy += dy * dy;
-    s_xy += dx * dy;
+  double n, s_x, s_y, s_xx, s_yy, s_xy;
+  auto accumulate = [&]() {
+    n = s_x = s_y = s_xx = s_yy = s_xy = 0.0;
+    for (int64_t row = r0 + threadIdx.x; row < r1; row += kBlock) {
+      if (!selected(row)) continue;
+      const double dx = as_double(X, row) - sx, dy = as_double(Y, row) - sy;
+      n += 1.0;
+      s_x += dx;
+      s_y += dy;
+      s_xx += dx * dx;
+      s_yy += dy * dy;
+      s_xy += dx * dy;
+    }
+  };
+  accumulate();
+  // The cancellation guard (moments_cancel, dq_scan_common.h), on the wave's sums: when the
+  // shift is an outlier in x or in y the wave sums its rows again about its own mean.  The cross
+  // term needs no test of its own: |Sx * Sy / n| = sqrt(qx * qy) <= kMomentCancel * sqrt(xMk * yMk)
+  // once neither side cancels, and ck is judged on that scale.
+  {
+    const double wn = wave_all_sum(n), w_x = wave_all_sum(s_x), w_y = wave_all_sum(s_y);
+    const double w_xx = wave_all_sum(s_xx), w_yy = wave_all_sum(s_yy);
+    if (wn > 0.0 && (moments_cancel(wn, w_x, w_xx) || moments_cancel(wn, w_y, w_yy))) {  // (wave-uniform)
+      const double mx = sx + w_x / wn, my = sy + w_y / wn;
+      if (fabs(mx) <= 0x1p1000 && fabs(my) <= 0x1p1000) {
+        sx = mx;
+        sy = my;
+        accumulate();
+      }
+    }
   }
   CorrAcc a;
   a.n = n;

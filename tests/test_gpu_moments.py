@@ -32,10 +32,12 @@ REL_TOL = 1e-12
 def _both_kernels(monkeypatch, fn):
     fn()                      # dq_scan_fast_kernel (no where, int64 / fp64)
     monkeypatch.setenv("DQ_SCAN_FAST", "0")
+    monkeypatch.setenv("DEEQU_AMD_PLAN_CACHE", "0")  # (the pooled plan of the first call keeps its kernels)
     try:
         fn()                  # dq_scan_values_kernel
     finally:
         monkeypatch.delenv("DQ_SCAN_FAST")
+        monkeypatch.delenv("DEEQU_AMD_PLAN_CACHE")
 
 
 def _stats(col, where=None):
@@ -94,6 +96,51 @@ def test_where_excludes_probed_outlier(gpu, monkeypatch, dtype):
         _check_state(a, st[a], ot)
 
 
+def _null_prefix_case(dtype, seed):
+    """30 000 NULL rows, then 90 000 values c + k / scale whose offset c is large against their
+    spread: a chunk that starts inside the prefix may find no shift near the data.  Returns the
+    device table and the exact (n, mean, m2, sum)."""
+    rng = np.random.default_rng(seed)
+    prefix, n = 30_000, 120_000
+    c, scale, spread = {"int64": (2 ** 24, 1, 4096), "int32": (2 ** 24, 1, 4096), "int16": (30000, 1, 512),
+                        "float64": (1000, 1024, 4096), "float32": (1000, 1024, 4096)}[dtype]
+    k = rng.integers(-spread, spread + 1, n - prefix)
+    vals = np.concatenate([np.zeros(prefix), c + k / scale]).astype(dtype)
+    assert np.array_equal(vals[prefix:].astype(np.float64), c + k / scale)  # exact in dtype
+    valid = np.arange(n) >= prefix
+    cnt, k_sum, k2_sum = n - prefix, int(k.sum()), int((k * k).sum())
+    mean = c + Fraction(k_sum, cnt * scale)
+    m2 = Fraction(k2_sum * cnt - k_sum * k_sum, cnt * scale * scale)
+    t = d.Table({"x": d.Column.from_numpy(vals, valid, dtype)}).to_device(0)
+    return t, cnt, float(mean), float(m2), float(mean * cnt)
+
+
+def _check_null_prefix(t, cnt, mean, m2, total):
+    sd, mn = d.StandardDeviation("x"), d.Mean("x")
+    st = d.run_scan([sd, mn], t)
+    assert st[sd].n == float(cnt) and st[mn].count == cnt
+    print("avg %.2e m2 %.2e sum %.2e" % (abs(st[sd].avg - mean) / mean, abs(st[sd].m2 - m2) / m2,
+                                         abs(st[mn].sum_value - total) / total))
+    assert abs(st[sd].avg - mean) <= REL_TOL * abs(mean), (st[sd].avg, mean)
+    assert abs(st[sd].m2 - m2) <= REL_TOL * abs(m2), (st[sd].m2, m2, abs(st[sd].m2 - m2) / m2)
+    assert abs(st[mn].sum_value - total) <= REL_TOL * abs(total), (st[mn].sum_value, total)
+
+
+@pytest.mark.parametrize("dtype", ["int64", "float64"])
+def test_null_prefix_then_offset_values(gpu, monkeypatch, dtype):
+    """2^24 + k as int64, 1000 + k/1024 as float64, on both kernels, against the exact moments
+    (test_gpu_fast_scan's test_null_prefix_then_values has data centred on 0, where a zero shift
+    is harmless)."""
+    case = _null_prefix_case(dtype, 31)
+    _both_kernels(monkeypatch, lambda: _check_null_prefix(*case))
+
+
+@pytest.mark.parametrize("dtype", ["int32", "float32", "int16"])
+def test_null_prefix_then_offset_values_narrow_types(gpu, dtype):
+    """The same through the general kernel's narrow types (int16: 30000 + k, |k| <= 512)."""
+    _check_null_prefix(*_null_prefix_case(dtype, 32))
+
+
 def _exact_from_ints(k_sum, k2_sum, n, scale):
     """mean, m2 of values k / scale given Σk, Σk² (Python ints)."""
     mean = Fraction(k_sum, n * scale)
@@ -131,6 +178,9 @@ def test_outlier_row0_at_scale(gpu, monkeypatch, dtype):
     col = d.Column(dtype, n, values.contiguous(), bits, device=True)
     t = d.Table({"x": col})
     del kv, vb
+    # the library reads the buffers on its plan's own stream: torch must have finished writing them
+    # (a fresh plan's allocations hid this; a pooled plan starts while `bits` is still being built)
+    torch.cuda.synchronize()
 
     def run():
         sd = d.StandardDeviation("x")
