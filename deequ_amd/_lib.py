@@ -19,6 +19,7 @@ LIB_PATH = os.environ.get("DEEQU_AMD_LIB") or os.path.join(
 DQ_OK, DQ_ERR_INVALID, DQ_ERR_UNSUPPORTED, DQ_ERR_DEVICE, DQ_ERR_OOM, DQ_ERR_STATE, DQ_ERR_SPACE = range(7)
 
 DQ_T_BOOL, DQ_T_INT8, DQ_T_INT16, DQ_T_INT32, DQ_T_INT64, DQ_T_FLOAT32, DQ_T_FLOAT64, DQ_T_UTF8 = range(1, 9)
+DQ_T_DECIMAL128 = 9
 DQ_COL_DEVICE = 0x1
 
 (DQ_OP_SIZE, DQ_OP_COMPLETENESS, DQ_OP_COMPLIANCE, DQ_OP_SUM, DQ_OP_MEAN, DQ_OP_STDDEV,
@@ -38,10 +39,55 @@ DQ_FREQ_NULL_AS_KEY = 0x1
 DQ_FREQ_FEW_ONLY = 0x2
 DQ_FLAT_DEVICE = 0x1
 
-TYPE_CODES = {
+import re as _re
+
+_DECIMAL_RE = _re.compile(r"^decimal\((\d+),(\d+)\)$")
+
+
+def decimal_type(precision: int, scale: int) -> int:
+    """DQ_T_DECIMAL(p, s): the int32 type code of a decimal column (include/deequ_amd.h)."""
+    return DQ_T_DECIMAL128 | (int(precision) << 8) | (int(scale) << 16)
+
+
+def decimal_params(dtype):
+    """(precision, scale) of the dtype string "decimal(p,s)" with precision 1..38 and scale 0..p,
+    else None."""
+    m = _DECIMAL_RE.match(dtype) if isinstance(dtype, str) else None
+    if not m:
+        return None
+    p, s = int(m.group(1)), int(m.group(2))
+    return (p, s) if 1 <= p <= 38 and s <= p else None
+
+
+def is_decimal(dtype) -> bool:
+    return decimal_params(dtype) is not None
+
+
+class _TypeCodes(dict):
+    """dtype string -> dq type code: the eight fixed names, and "decimal(p,s)" parsed on lookup."""
+
+    def __missing__(self, dtype):
+        ps = decimal_params(dtype)
+        if ps is None:
+            raise KeyError(dtype)
+        return decimal_type(*ps)
+
+    def __contains__(self, dtype):
+        return dict.__contains__(self, dtype) or is_decimal(dtype)
+
+
+TYPE_CODES = _TypeCodes({
     "bool": DQ_T_BOOL, "int8": DQ_T_INT8, "int16": DQ_T_INT16, "int32": DQ_T_INT32,
     "int64": DQ_T_INT64, "float32": DQ_T_FLOAT32, "float64": DQ_T_FLOAT64, "string": DQ_T_UTF8,
-}
+})
+
+
+class NumericTypes(tuple):
+    """The dtypes Preconditions.isNumeric accepts (Analyzer.scala:336): the six fixed names and
+    every "decimal(p,s)"."""
+
+    def __contains__(self, dtype):
+        return tuple.__contains__(self, dtype) or is_decimal(dtype)
 
 
 class DqColumn(Structure):
@@ -145,6 +191,8 @@ DIAG_SIGNATURES = {
                                    POINTER(c_int64)]),
     "dq_diag_schema_cell": (c_int, [c_int32, c_char_p, c_int64, c_int32, c_int32, POINTER(c_int32),
                                     POINTER(c_int64)]),
+    "dq_diag_decimal_to_double": (c_int, [c_uint64, c_int64, c_int32, POINTER(c_double), POINTER(c_int32)]),
+    "dq_diag_decimal_bytes": (c_int, [c_uint64, c_int64, c_char_p, POINTER(c_int32)]),
 }
 
 
@@ -198,6 +246,7 @@ SIGNATURES = {
                                     POINTER(c_int64), POINTER(c_int64)]),
     "dq_freq_import_flat": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int]),
     "dq_cast_utf8": (c_int, [c_void_p, POINTER(DqColumn), c_int64, c_int32, c_void_p, c_void_p, POINTER(c_int64)]),
+    "dq_cast_decimal": (c_int, [c_void_p, POINTER(DqColumn), c_int64, c_void_p, c_void_p]),
     "dq_cast_utf8_batch": (c_int, [c_void_p, c_int32, POINTER(DqColumn), c_int64, POINTER(c_int32),
                                    POINTER(c_void_p), POINTER(c_void_p)]),
     "dq_profile_few_strings": (c_int, [c_void_p, c_int32, POINTER(DqColumn), c_int64, POINTER(DqFewResult),

@@ -25,7 +25,7 @@ from .metrics import (DoubleMetric, Entity, Failure, IllegalAnalyzerParameterExc
 from . import engine as _engine
 from .states import State, merge, state_from_dq
 
-NUMERIC_TYPES = ("int8", "int16", "int32", "int64", "float32", "float64")
+NUMERIC_TYPES = L.NumericTypes(("int8", "int16", "int32", "int64", "float32", "float64"))
 
 
 def _opt(x: Optional[str]) -> str:
@@ -156,6 +156,11 @@ class ScanShareableAnalyzer(Analyzer):
     def metricFromAggregationResult(self, raw, aggregateWith=None, saveStatesWith=None):
         """Analyzer.metricFromAggregationResult (Analyzer.scala:185-195)."""
         return self.calculateMetric(self.fromAggregationResult(raw), aggregateWith, saveStatesWith)
+
+    def castsDecimals(self, schema) -> bool:
+        """True when the analyzer runs over the float64 cast of a decimal column (decimals.py), in a
+        scan of its own instead of the shared one."""
+        return False
 
     def computeStateFrom(self, data) -> Optional[State]:
         from .engine import run_scan
@@ -388,6 +393,19 @@ class Correlation(StandardScanShareableAnalyzer):
     def additionalPreconditions(self):
         return [Preconditions.hasColumn(self.firstColumn), Preconditions.isNumeric(self.firstColumn),
                 Preconditions.hasColumn(self.secondColumn), Preconditions.isNumeric(self.secondColumn)]
+
+    def castsDecimals(self, schema) -> bool:
+        return any(L.is_decimal(schema.get(c)) for c in (self.firstColumn, self.secondColumn))
+
+    def computeStateFrom(self, data) -> Optional[State]:
+        # Corr takes DoubleType: a decimal operand is cast row by row first (Decimal.toDouble), here by
+        # dq_cast_decimal into a float64 column the pair kernel then reads like any other
+        from .decimals import float64_view
+        from .engine import run_scan, schema_index
+        from .predicates import compile_predicate
+        if self.where and self.castsDecimals(data.schema):  # the filter is typed against the real schema
+            compile_predicate(self.where, schema_index(data.schema))
+        return run_scan([self], float64_view(data, [self.firstColumn, self.secondColumn]))[self]
 
     def __str__(self):
         return "Correlation(%s,%s,%s)" % (self.firstColumn, self.secondColumn, _opt(self.where))

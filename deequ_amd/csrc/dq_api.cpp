@@ -24,6 +24,7 @@
 #include "dq_keypack.h"
 #include "dq_uuidpack.h"
 #include "dq_numparse.h"
+#include "dq_decimal.h"
 #include "dq_predeval.h"
 #include "dq_regex.h"
 #include "dq_kll.h"
@@ -60,7 +61,14 @@ extern "C" const char* dq_last_error(void) { return g_last_error.c_str(); }
 extern "C" int dq_abi_version(void) { return DQ_ABI_VERSION; }
 
 // ------------------------------------------------------------------------------ helpers
+static bool is_decimal(int t) { return DQ_T_BASE(t) == DQ_T_DECIMAL128; }
+// DQ_T_DECIMAL(p, s) with precision 1..38 and scale 0..p, nothing above the scale byte
+static bool valid_decimal(int t) {
+  return is_decimal(t) && t > 0 && (t >> 24) == 0 && DQ_T_PRECISION(t) >= 1 &&
+         DQ_T_PRECISION(t) <= dec::kMaxPrecision && DQ_T_SCALE(t) <= DQ_T_PRECISION(t);
+}
 static int type_size(int t) {
+  if (is_decimal(t)) return 16;
   switch (t) {
     case DQ_T_INT8: return 1;
     case DQ_T_INT16: return 2;
@@ -73,7 +81,10 @@ static int type_size(int t) {
 }
 static bool is_numeric(int t) { return t >= DQ_T_INT8 && t <= DQ_T_FLOAT64; }
 static bool is_integral(int t) { return t >= DQ_T_INT8 && t <= DQ_T_INT64; }
-static bool valid_type(int t) { return t >= DQ_T_BOOL && t <= DQ_T_UTF8; }
+static bool valid_type(int t) { return (t >= DQ_T_BOOL && t <= DQ_T_UTF8) || valid_decimal(t); }
+static std::string decimal_name(int t) {
+  return "decimal(" + std::to_string(DQ_T_PRECISION(t)) + "," + std::to_string(DQ_T_SCALE(t)) + ")";
+}
 
 // Device block pool.  hipMalloc / hipFree of multi-GB buffers cost milliseconds to seconds, and
 // every hipFree synchronises the device -- a profiler run creates and drops dozens of small
@@ -412,7 +423,8 @@ extern "C" dq_status dq_ctx_destroy(dq_ctx* ctx) {
 // Value types of the validator.  V_F32 is a FloatType value (a FLOAT32 column or a cast to
 // FLOAT32; the device holds it as the fp64 of the same value); V_NULL the untyped NULL literal,
 // compatible with every type (Spark types it by the other side).
-enum VT { V_INT = 0, V_FLT = 1, V_BOOL = 2, V_STR = 3, V_F32 = 4, V_NULL = 5 };
+// V_DEC is a decimal column's value: only IS [NOT] NULL takes it.
+enum VT { V_INT = 0, V_FLT = 1, V_BOOL = 2, V_STR = 3, V_F32 = 4, V_NULL = 5, V_DEC = 6 };
 
 struct Program {
   std::vector<PredInsn> code;
@@ -425,7 +437,12 @@ static bool vt_fractional(int t) { return t == V_FLT || t == V_F32; }
 
 // The binary-operand rules of the header's "Type rules" (include/deequ_amd.h): a pair the IR
 // cannot evaluate exactly as Spark 2.2 would is DQ_ERR_UNSUPPORTED.
+static dq_status decimal_expression() {
+  return fail(DQ_ERR_UNSUPPORTED, "decimal-typed expression (a decimal column takes only IS [NOT] NULL on the GPU)");
+}
+
 static dq_status check_pair(int a, int b, const char* what) {
+  if (a == V_DEC || b == V_DEC) return decimal_expression();
   if (a == V_NULL || b == V_NULL) return DQ_OK;
   if ((a == V_STR) != (b == V_STR))  // Spark casts the string: only DQ_P_CAST_DOUBLE does that
     return fail(DQ_ERR_UNSUPPORTED, std::string(what) + " of a string with a non-string");
@@ -448,7 +465,7 @@ static dq_status validate_predicate(const dq_predicate& p, const int32_t* types,
       case DQ_P_COLUMN: {
         if (in.arg < 0 || in.arg >= n_cols) return fail(DQ_ERR_INVALID, "predicate column out of range");
         const int t = types[in.arg];
-        st.push_back(t == DQ_T_UTF8 ? V_STR : t == DQ_T_BOOL ? V_BOOL : t == DQ_T_FLOAT32 ? V_F32
+        st.push_back(is_decimal(t) ? V_DEC : t == DQ_T_UTF8 ? V_STR : t == DQ_T_BOOL ? V_BOOL : t == DQ_T_FLOAT32 ? V_F32
                      : (is_integral(t) ? V_INT : V_FLT));
         prog.columns.push_back(in.arg);
         break;
@@ -464,6 +481,7 @@ static dq_status validate_predicate(const dq_predicate& p, const int32_t* types,
       case DQ_P_LIT_NULL: st.push_back(V_NULL); break;
       case DQ_P_CAST_DOUBLE:  // Cast(-> DoubleType) of a string or a number
         if (st.empty()) return fail(DQ_ERR_INVALID, "predicate stack underflow");
+        if (st.back() == V_DEC) return decimal_expression();
         if (st.back() == V_BOOL) return fail(DQ_ERR_UNSUPPORTED, "cast of a boolean to double");
         if (st.back() != V_NULL) st.back() = V_FLT;
         break;
@@ -480,6 +498,7 @@ static dq_status validate_predicate(const dq_predicate& p, const int32_t* types,
             return fail(DQ_ERR_UNSUPPORTED, "DQ_P_CAST to type " + std::to_string(to) +
                         " (only INT8..INT64, FLOAT32, FLOAT64 and BOOL are evaluated on the GPU)");
         }
+        if (st.back() == V_DEC) return decimal_expression();
         if (st.back() == V_STR)
           return fail(DQ_ERR_UNSUPPORTED, "DQ_P_CAST of a string (Spark's UTF8String casts stay on Spark)");
         if (st.back() != V_NULL) st.back() = vt;
@@ -490,6 +509,7 @@ static dq_status validate_predicate(const dq_predicate& p, const int32_t* types,
         if (st.size() < 2) return fail(DQ_ERR_INVALID, "predicate stack underflow");
         const int b = st.back(); st.pop_back();
         const int a = st.back(); st.pop_back();
+        if (a == V_DEC || b == V_DEC) return decimal_expression();
         if (a != V_NULL && b != V_NULL && (a == V_BOOL) != (b == V_BOOL))
           return fail(DQ_ERR_UNSUPPORTED, "COALESCE of mixed boolean/numeric");
         DQ_TRY(check_pair(a, b, "COALESCE"));
@@ -509,6 +529,7 @@ static dq_status validate_predicate(const dq_predicate& p, const int32_t* types,
         const int a = st.back(); st.pop_back();
         if (in.arg != DQ_CMP_AS_INT64 && in.arg != DQ_CMP_AS_FLOAT64)
           return fail(DQ_ERR_INVALID, "comparison type must be DQ_CMP_AS_INT64 or DQ_CMP_AS_FLOAT64");
+        if (a == V_DEC || b == V_DEC) return decimal_expression();
         if (in.arg == DQ_CMP_AS_INT64 && (vt_fractional(a) || vt_fractional(b)))
           return fail(DQ_ERR_UNSUPPORTED, "int64 comparison of a floating-point operand (Spark compares "
                       "that pair in a fractional type: cast it or compare as DQ_CMP_AS_FLOAT64)");
@@ -537,6 +558,7 @@ static dq_status validate_predicate(const dq_predicate& p, const int32_t* types,
     if ((int)st.size() > kMaxStack) return fail(DQ_ERR_UNSUPPORTED, "predicate stack too deep");
     prog.code.push_back(pi);
   }
+  if (st.size() == 1 && st.back() == V_DEC) return decimal_expression();
   if (st.size() != 1 || st.back() != V_BOOL)
     return fail(DQ_ERR_INVALID, "predicate must leave exactly one boolean");
   std::sort(prog.columns.begin(), prog.columns.end());
@@ -724,7 +746,7 @@ static bool fast_variant(ScanTask* t, int* variant) {
 }
 
 // ------------------------------------------------------------------------------ plan
-enum Target { TGT_HOST_SIZE = 0, TGT_SCAN = 1, TGT_HLL = 2, TGT_DTYPE = 3, TGT_STRLEN = 4, TGT_CORR = 5, TGT_REGEX = 6 };
+enum Target { TGT_HOST_SIZE = 0, TGT_SCAN = 1, TGT_HLL = 2, TGT_DTYPE = 3, TGT_STRLEN = 4, TGT_CORR = 5, TGT_REGEX = 6, TGT_DEC = 7 };
 
 struct OpSlot {
   int kind;
@@ -795,6 +817,8 @@ struct dq_plan : Stager {
   std::vector<HllTask> hll_launch, dtype_launch;
   std::vector<HllTask> len_tasks;    // MinLength / MaxLength: {column, type, where}
   std::vector<CorrTask> corr_tasks;  // Correlation: {x, y, where}
+  std::vector<DecTask> dec_tasks;    // decimal columns: every scan-shareable op of one (column, where)
+  int dec_per_cu = -1;               // resident workgroups per CU of the decimal scan (-1 = not asked yet)
   // PatternMatch: {column, where, DFA}; the distinct patterns' images back to back in d_rx_dfas
   std::vector<RegexTask> regex_tasks;
   std::vector<std::string> regex_patterns;
@@ -804,9 +828,11 @@ struct dq_plan : Stager {
   std::vector<Program> programs;  // generic predicate programs -> batch masks
   // device state
   std::vector<dq_status> op_status;  // per op, after dq_plan_finish
+  std::vector<std::string> op_message;  // ... and what dq_plan_op_status says ("" = the predicate cast's text)
   bool pred_cast = false;  // a predicate program casts a string to double (its own kernel: the parser's scratch)
   DevBuf d_tasks, d_groups, d_ranges, d_hll, d_progs, d_insns, d_pool, d_acc, d_partials, d_regs,
-      d_cols, d_masks, d_mask_words, d_dtype, d_dtype_counts, d_len, d_len_out, d_corr, d_corr_part, d_corr_acc, d_str, d_rx, d_rx_dfas, d_rx_out;
+      d_cols, d_masks, d_mask_words, d_dtype, d_dtype_counts, d_len, d_len_out, d_corr, d_corr_part, d_corr_acc, d_str, d_rx, d_rx_dfas, d_rx_out,
+      d_dec, d_dec_acc, d_dec_part;
   int64_t mask_words = 0;
   // pinned descriptor staging (DevColumn + DevMask arrays) guarded by an event
   void* h_desc = nullptr;
@@ -854,8 +880,15 @@ static dq_status check_op(const dq_op& op, const int32_t* types, int n_cols, reg
   auto need_col = [&](bool numeric) -> dq_status {
     if (op.column < 0 || op.column >= n_cols) return fail(DQ_ERR_INVALID, "op column out of range");
     if (!valid_type(types[op.column])) return fail(DQ_ERR_INVALID, "invalid column type");
-    if (numeric && !is_numeric(types[op.column]))
+    if (numeric && !is_numeric(types[op.column]) && !is_decimal(types[op.column]))
       return fail(DQ_ERR_UNSUPPORTED, "analyzer needs a numeric column (Preconditions.isNumeric)");
+    return DQ_OK;
+  };
+  // the ops the decimal scan serves; every other op on a decimal column stays on Spark
+  auto no_decimal = [&](int column, const char* what) -> dq_status {
+    if (column >= 0 && column < n_cols && is_decimal(types[column]))
+      return fail(DQ_ERR_UNSUPPORTED, std::string(what) + " of a " + decimal_name(types[column]) +
+                  " column is not on the GPU path (Correlation runs over dq_cast_decimal's float64 column)");
     return DQ_OK;
   };
   switch (op.kind) {
@@ -868,7 +901,7 @@ static dq_status check_op(const dq_op& op, const int32_t* types, int n_cols, reg
       DQ_TRY(need_col(true));
       break;
     case DQ_OP_APPROX_COUNT_DISTINCT: DQ_TRY(need_col(false)); break;
-    case DQ_OP_DATATYPE: DQ_TRY(need_col(false)); break;
+    case DQ_OP_DATATYPE: DQ_TRY(need_col(false)); DQ_TRY(no_decimal(op.column, "DataType")); break;
     case DQ_OP_MIN_LENGTH: case DQ_OP_MAX_LENGTH:
       DQ_TRY(need_col(false));
       if (types[op.column] != DQ_T_UTF8)
@@ -890,6 +923,9 @@ static dq_status check_op(const dq_op& op, const int32_t* types, int n_cols, reg
     case DQ_OP_CORRELATION:
       DQ_TRY(need_col(true));
       if (op.column2 < 0 || op.column2 >= n_cols) return fail(DQ_ERR_INVALID, "op column2 out of range");
+      if (!valid_type(types[op.column2])) return fail(DQ_ERR_INVALID, "invalid column type");
+      DQ_TRY(no_decimal(op.column, "Correlation"));
+      DQ_TRY(no_decimal(op.column2, "Correlation"));
       if (!is_numeric(types[op.column2]))
         return fail(DQ_ERR_UNSUPPORTED, "analyzer needs a numeric column (Preconditions.isNumeric)");
       break;
@@ -946,6 +982,14 @@ extern "C" dq_status dq_plan_create(dq_ctx* ctx, const dq_op* ops, int n_ops,
     return (int)tasks.size() - 1;
   };
 
+  auto find_or_add_dec = [&](int column, int where_prog) -> int {
+    for (size_t i = 0; i < plan->dec_tasks.size(); ++i)
+      if (plan->dec_tasks[i].column == column && plan->dec_tasks[i].where_mask == where_prog) return (int)i;
+    const int t = column_types[column];
+    plan->dec_tasks.push_back(DecTask{column, where_prog, 0, 0, DQ_T_PRECISION(t), DQ_T_SCALE(t), {0, 0}});
+    return (int)plan->dec_tasks.size() - 1;
+  };
+
   dq_status st = DQ_OK;
   for (int i = 0; i < n_ops && st == DQ_OK; ++i) {
     const dq_op& op = ops[i];
@@ -973,10 +1017,21 @@ extern "C" dq_status dq_plan_create(dq_ctx* ctx, const dq_op* ops, int n_ops,
       }
       case DQ_OP_COMPLETENESS:
         plan->col_used[op.column] = true;
+        if (is_decimal(column_types[op.column])) {  // rides on the column's decimal scan
+          slot.target = TGT_DEC;
+          slot.task = find_or_add_dec(op.column, where_prog);
+          break;
+        }
         slot.task = find_or_add_task(op.column, where_prog);
         break;
       case DQ_OP_SUM: case DQ_OP_MEAN: case DQ_OP_STDDEV: case DQ_OP_MINIMUM: case DQ_OP_MAXIMUM: {
         plan->col_used[op.column] = true;
+        if (is_decimal(column_types[op.column])) {
+          slot.target = TGT_DEC;
+          slot.task = find_or_add_dec(op.column, where_prog);
+          plan->dec_tasks[slot.task].flags |= DF_STATS;
+          break;
+        }
         slot.task = find_or_add_task(op.column, where_prog);
         tasks[slot.task].t.flags |= TF_VALUES | TF_STATS;
         break;
@@ -1029,7 +1084,11 @@ extern "C" dq_status dq_plan_create(dq_ctx* ctx, const dq_op* ops, int n_ops,
         if (t < 0) {
           t = (int)plan->hll_sets.size();
           plan->hll_sets.emplace_back(op.column, where_prog);
-          if (is_numeric(column_types[op.column])) {  // hashed in the column's value scan
+          if (is_decimal(column_types[op.column])) {  // hashed in the column's decimal scan
+            const int dt = find_or_add_dec(op.column, where_prog);
+            plan->dec_tasks[dt].flags |= DF_HLL;
+            plan->dec_tasks[dt].hll = t;
+          } else if (is_numeric(column_types[op.column])) {  // hashed in the column's value scan
             const int st_ = find_or_add_task(op.column, where_prog);
             tasks[st_].t.flags |= TF_VALUES | TF_HLL;
             tasks[st_].t.hll = t;
@@ -1211,6 +1270,8 @@ extern "C" dq_status dq_plan_create(dq_ctx* ctx, const dq_op* ops, int n_ops,
       (s = upload(plan->d_rx, plan->regex_tasks.data(), plan->regex_tasks.size() * sizeof(RegexTask))) != DQ_OK ||
       (s = upload(plan->d_rx_dfas, plan->regex_images.data(), plan->regex_images.size())) != DQ_OK ||
       (s = plan->d_rx_out.ensure(std::max<size_t>(1, plan->regex_tasks.size()) * 2 * sizeof(uint64_t))) != DQ_OK ||
+      (s = upload(plan->d_dec, plan->dec_tasks.data(), plan->dec_tasks.size() * sizeof(DecTask))) != DQ_OK ||
+      (s = plan->d_dec_acc.ensure(std::max<size_t>(1, plan->dec_tasks.size()) * sizeof(DecAcc))) != DQ_OK ||
       (s = upload(plan->d_progs, progs.data(), progs.size() * sizeof(PredProgram))) != DQ_OK ||
       (s = upload(plan->d_insns, insns.data(), insns.size() * sizeof(PredInsn))) != DQ_OK ||
       (s = upload(plan->d_pool, pool.data(), pool.size())) != DQ_OK ||
@@ -1270,6 +1331,8 @@ extern "C" dq_status dq_plan_op_status(dq_plan* plan, int op) {
   if (!plan) return fail(DQ_ERR_INVALID, "plan is NULL");
   if (op < 0 || op >= (int)plan->slots.size()) return fail(DQ_ERR_INVALID, "op index out of range");
   if (plan->op_status.size() != plan->slots.size()) return fail(DQ_ERR_STATE, "dq_plan_finish has not run");
+  if (plan->op_status[op] != DQ_OK && op < (int)plan->op_message.size() && !plan->op_message[op].empty())
+    return fail(plan->op_status[op], plan->op_message[op]);
   if (plan->op_status[op] != DQ_OK)
     return fail(plan->op_status[op], "a string -> double cast in this op's predicate met a number off the exact "
                                      "fast path (> 19 significant digits, |exponent| > 22 or hex): route it to Spark");
@@ -1300,6 +1363,7 @@ extern "C" dq_status dq_plan_reset(dq_plan* plan) {
     DQ_HIP(hipMemsetAsync(plan->d_len_out.ptr, 0, plan->len_tasks.size() * 3 * sizeof(uint64_t), plan->stream));
   if (!plan->regex_tasks.empty())
     DQ_HIP(hipMemsetAsync(plan->d_rx_out.ptr, 0, plan->regex_tasks.size() * 2 * sizeof(uint64_t), plan->stream));
+  DQ_HIP(launch_init_dec_acc(static_cast<DecAcc*>(plan->d_dec_acc.ptr), (int)plan->dec_tasks.size(), plan->stream));
   if (!plan->corr_tasks.empty())  // all-zero CorrAcc = the empty state (n = 0)
     DQ_HIP(hipMemsetAsync(plan->d_corr_acc.ptr, 0, plan->corr_tasks.size() * sizeof(CorrAcc), plan->stream));
   DQ_HIP(hipStreamSynchronize(plan->stream));
@@ -1592,6 +1656,21 @@ extern "C" dq_status dq_plan_consume(dq_plan* plan, const dq_column* columns, in
                        static_cast<CorrAcc*>(plan->d_corr_part.ptr), static_cast<CorrAcc*>(plan->d_corr_acc.ptr),
                        plan->stream));
   }
+  const int n_dec = (int)plan->dec_tasks.size();
+  if (n_dec > 0) {  // whole rounds of resident workgroups, split over the tasks (as the value scans)
+    if (plan->dec_per_cu < 0) plan->dec_per_cu = scan_dec_blocks_per_cu();
+    int64_t bpt = std::max<int64_t>(1, plan->target_blocks / n_dec);
+    if (plan->n_cu > 0 && plan->dec_per_cu > 0 && plan->scan_rounds > 0)
+      bpt = std::max<int64_t>(1, (int64_t)plan->n_cu * plan->dec_per_cu * plan->scan_rounds / n_dec);
+    bpt = std::max<int64_t>(1, std::min<int64_t>(bpt, chunks));
+    // a block's limb sums hold 2^31 rows: keep its span <= 2^27 rows like the other scans
+    bpt = std::max<int64_t>(bpt, (chunks + (((int64_t)1 << 27) / kScanRowAlign) - 1) /
+                                     (((int64_t)1 << 27) / kScanRowAlign));
+    DQ_TRY(plan->d_dec_part.ensure((size_t)n_dec * (size_t)bpt * sizeof(DecAcc)));
+    DQ_HIP(launch_scan_dec(static_cast<const DecTask*>(plan->d_dec.ptr), n_dec, d_cols, d_masks, n_rows, (int)bpt,
+                           static_cast<DecAcc*>(plan->d_dec_part.ptr), static_cast<DecAcc*>(plan->d_dec_acc.ptr),
+                           static_cast<uint32_t*>(plan->d_regs.ptr), plan->stream));
+  }
   if (side) DQ_HIP(hipStreamWaitEvent(plan->stream, plan->side_done, 0));
   plan->total_rows += n_rows;
   DQ_HIP(hipEventRecord(plan->scan_done[slot], plan->stream));
@@ -1631,6 +1710,7 @@ extern "C" dq_status dq_plan_finish(dq_plan* plan, dq_state* out, int n_out) {
   std::vector<uint64_t> lens(plan->len_tasks.size() * 3);
   std::vector<CorrAcc> corr(plan->corr_tasks.size());
   std::vector<uint64_t> rx(plan->regex_tasks.size() * 2);
+  std::vector<DecAcc> dacc(plan->dec_tasks.size());
   // every result array comes back in ONE pass through a pinned bounce buffer (pageable copies
   // are staged by the runtime, tens of microseconds each), then one synchronize
   struct Back {
@@ -1643,6 +1723,7 @@ extern "C" dq_status dq_plan_finish(dq_plan* plan, dq_state* out, int n_out) {
                         {corr.data(), plan->d_corr_acc.ptr, corr.size() * sizeof(CorrAcc)},
                         {dtc.data(), plan->d_dtype_counts.ptr, dtc.size() * sizeof(uint64_t)},
                         {acc.data(), plan->d_acc.ptr, acc.size() * sizeof(ScanAcc)},
+                        {dacc.data(), plan->d_dec_acc.ptr, dacc.size() * sizeof(DecAcc)},
                         {regs.data(), plan->d_regs.ptr, regs.size() * sizeof(uint32_t)}};
   size_t total = 0;
   for (const Back& b : backs) total += (b.bytes + 255) & ~(size_t)255;
@@ -1667,6 +1748,7 @@ extern "C" dq_status dq_plan_finish(dq_plan* plan, dq_state* out, int n_out) {
     at += (b.bytes + 255) & ~(size_t)255;
   }
   plan->op_status.assign(plan->slots.size(), DQ_OK);
+  plan->op_message.assign(plan->slots.size(), std::string());
   plan->desc_pending = false;
   plan->host_tmp.clear();
 
@@ -1712,6 +1794,53 @@ extern "C" dq_status dq_plan_finish(dq_plan* plan, dq_state* out, int n_out) {
     if (s.target == TGT_HLL) {  // never NULL (StatefulHyperloglogPlus.nullable = false)
       o.has_value = 1;
       pack_hll(&regs[(size_t)s.task * kHllM], o.words);
+      continue;
+    }
+    if (s.target == TGT_DEC) {
+      const DecAcc& a = dacc[s.task];
+      const DecTask& t = plan->dec_tasks[s.task];
+      const bool count_ok = s.has_where ? (a.n_wnn > 0) : true;
+      switch (s.kind) {
+        case DQ_OP_COMPLETENESS:
+          o.has_value = (rows > 0 && count_ok) ? 1 : 0;
+          o.num_matches = a.n_sel;
+          o.count = s.has_where ? a.n_rows : rows;
+          break;
+        case DQ_OP_SUM: case DQ_OP_MEAN: {
+          // sum(decimal(p, s)) is a decimal(min(38, p + 10), s) (Spark 2.2.2 Sum.resultType); while
+          // Σ|x| stays below 10^min(38, p + 10) no prefix of the rows in any order leaves it, so the
+          // exact sum is Spark's answer; at or beyond it Spark's result depends on the order
+          // (SPARK-28067): declined, never approximated
+          const dec::u128 bound = dec::pow10_u128(std::min(dec::kMaxPrecision, t.precision + 10));
+          if (a.n_sel > 0 && (a.abs[2] != 0 || dec::make_u128(a.abs[0], a.abs[1]) >= bound)) {
+            plan->op_status[i] = DQ_ERR_UNSUPPORTED;
+            plan->op_message[i] = "the sum of |x| over the " + decimal_name(plan->col_types[t.column]) +
+                                  " column reaches 10^" + std::to_string(std::min(dec::kMaxPrecision, t.precision + 10)) +
+                                  ": Spark's decimal sum may overflow depending on the row order (SPARK-28067); "
+                                  "route this analyzer to Spark";
+            break;
+          }
+          o.has_value = a.n_sel > 0;
+          o.sum = dec::to_double(a.sum[0], (int64_t)a.sum[1], t.scale);  // (|sum| <= Σ|x| < 2^127)
+          if (s.kind == DQ_OP_MEAN) o.count = a.n_sel;
+          break;
+        }
+        case DQ_OP_STDDEV:
+          o.has_value = a.n_sel > 0;
+          o.n = (double)a.n_sel;
+          o.avg = a.mean;
+          o.m2 = a.m2;
+          break;
+        case DQ_OP_MINIMUM:
+          o.has_value = a.n_sel > 0;
+          o.value = dec::to_double(a.min_lo, a.min_hi, t.scale);
+          break;
+        case DQ_OP_MAXIMUM:
+          o.has_value = a.n_sel > 0;
+          o.value = dec::to_double(a.max_lo, a.max_hi, t.scale);
+          break;
+        default: break;
+      }
       continue;
     }
     const ScanAcc& a = acc[s.task];
@@ -2012,6 +2141,22 @@ extern "C" dq_status dq_diag_parse_double(const uint8_t* s, int64_t n, double* o
   return DQ_OK;
 }
 
+extern "C" dq_status dq_diag_decimal_to_double(uint64_t lo, int64_t hi, int32_t scale, double* out, int32_t* tier) {
+  if (!out || scale < 0 || scale > dec::kMaxPrecision) return fail(DQ_ERR_INVALID, "bad argument");
+  *out = dec::to_double(lo, hi, scale);
+  if (tier) *tier = dec::tier_of(dec::magnitude(lo, hi), scale);
+  return DQ_OK;
+}
+
+extern "C" dq_status dq_diag_decimal_bytes(uint64_t lo, int64_t hi, uint8_t* out, int32_t* len) {
+  if (!out || !len) return fail(DQ_ERR_INVALID, "bad argument");
+  const int n = dec::byte_length(lo, hi);
+  const dec::u128 st = dec::be_stream(lo, hi, n);
+  for (int j = 0; j < n; ++j) out[j] = (uint8_t)(st >> (8 * j));
+  *len = n;
+  return DQ_OK;
+}
+
 // Host build of PatternMatch's regex engine (dq_regex.h): the compiler check_op runs, and the walker
 // dq_regex_kernel runs.
 extern "C" dq_status dq_diag_regex_match(const uint8_t* pattern, int32_t pattern_len, const uint8_t* text, int64_t n,
@@ -2118,6 +2263,29 @@ extern "C" dq_status dq_cast_utf8(dq_ctx* ctx, const dq_column* src, int64_t n_r
   st.stream = nullptr;
   if (s != DQ_OK) return s;
   if (e != hipSuccess) return fail(DQ_ERR_DEVICE, std::string("dq_cast_utf8: ") + hipGetErrorString(e));
+  return DQ_OK;
+}
+
+extern "C" dq_status dq_cast_decimal(dq_ctx* ctx, const dq_column* src, int64_t n_rows, double* d_values_f64,
+                                     uint8_t* d_validity) {
+  if (!ctx || !src || (n_rows > 0 && (!d_values_f64 || !d_validity))) return fail(DQ_ERR_INVALID, "NULL argument");
+  if (!valid_decimal(src->type)) return fail(DQ_ERR_INVALID, "dq_cast_decimal needs a decimal column");
+  if (n_rows < 0 || src->length < n_rows) return fail(DQ_ERR_INVALID, "bad n_rows");
+  if (n_rows == 0) return DQ_OK;
+  DQ_HIP(hipSetDevice(ctx->device));
+  Stager st;
+  DQ_HIP(StreamPool::get().acquire(ctx->device, &st.stream));
+  st.col_types.assign(1, src->type);
+  st.resize_stage(1);
+  DevColumn dc;
+  dq_status s = prepare_column(&st, 0, *src, n_rows, &dc);
+  hipError_t e = hipSuccess;
+  if (s == DQ_OK) e = launch_cast_decimal(dc, DQ_T_SCALE(src->type), n_rows, d_values_f64, d_validity, st.stream);
+  if (s == DQ_OK && e == hipSuccess) e = hipStreamSynchronize(st.stream);
+  StreamPool::get().release(ctx->device, st.stream);
+  st.stream = nullptr;
+  if (s != DQ_OK) return s;
+  if (e != hipSuccess) return fail(DQ_ERR_DEVICE, std::string("dq_cast_decimal: ") + hipGetErrorString(e));
   return DQ_OK;
 }
 

@@ -1191,6 +1191,12 @@ extern "C" dq_status dq_freq_create(dq_ctx* ctx, const int32_t* key_columns, int
       delete f;
       return fail(DQ_ERR_INVALID, "grouping column out of range");
     }
+    if (is_decimal(column_types[key_columns[i]])) {  // (no key encoding of decimals: DESIGN.md §7)
+      delete f;
+      return fail(DQ_ERR_UNSUPPORTED, "grouping column " + std::to_string(key_columns[i]) + " is a " +
+                                          decimal_name(column_types[key_columns[i]]) +
+                                          " column: decimal keys are not on the GPU path");
+    }
     f->ks.key_cols[i] = key_columns[i];
     f->col_used[key_columns[i]] = true;
     f->has_utf8 = f->has_utf8 || column_types[key_columns[i]] == DQ_T_UTF8;

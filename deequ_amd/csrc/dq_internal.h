@@ -147,6 +147,33 @@ struct CorrAcc {
   double n, xavg, yavg, ck, xmk, ymk;
 };
 
+// Decimal scan task (dq_scan_dec.hip): every scan-shareable analyzer of one decimal (column, where)
+// and the per-(task, block) partial / per-task running accumulator.  Every DecAcc field is 8 bytes.
+enum DecTaskFlags : int32_t {
+  DF_STATS = 1,  // Sum / Mean / Minimum / Maximum / StandardDeviation wanted
+  DF_HLL = 2     // ApproxCountDistinct wanted
+};
+struct DecTask {
+  int32_t column;
+  int32_t where_mask;  // -1 = none
+  int32_t flags;       // DecTaskFlags
+  int32_t hll;         // DF_HLL: the register set (registers + hll * kHllM)
+  int32_t precision, scale;
+  int32_t pad[2];
+};
+struct DecAcc {
+  int64_t n_rows;   // Σ where TRUE (or all rows)
+  int64_t n_wnn;    // Σ where NOT NULL (or all rows)
+  int64_t n_sel;    // Σ valid & where TRUE
+  uint64_t sum[3];  // exact Σ x of the selected unscaled values: 192-bit two's complement
+  uint64_t abs[3];  // exact Σ |x|
+  uint64_t min_lo;  // signed 128-bit minimum / maximum of the selected values
+  int64_t min_hi;   // (n_sel = 0: min = 2^127 - 1, max = -2^127)
+  uint64_t max_lo;
+  int64_t max_hi;
+  double mean, m2;  // moments of the values cast to double, about their mean
+};
+
 // One instruction of the generic predicate interpreter (dq_pred_insn after validation).
 struct PredInsn {
   int32_t opcode;
@@ -516,6 +543,17 @@ hipError_t launch_corr(const CorrTask* d_tasks, int n_tasks, const DevColumn* d_
                        hipStream_t stream);
 hipError_t launch_cast_utf8(const DevColumn& src, int64_t n_rows, int to_type, void* d_values, uint8_t* d_validity,
                             hipStream_t stream);
+// The decimal scan (dq_scan_dec.hip): grid (blocks_per_task, n_tasks), partial of (task i, block b)
+// at d_partials[i * blocks_per_task + b]; then one block per task merges them in block order and
+// folds the batch into d_acc[i].  Registers of DF_HLL tasks are raised in d_hll_regs.
+hipError_t launch_scan_dec(const DecTask* d_tasks, int n_tasks, const DevColumn* d_cols, const DevMask* d_masks,
+                           int64_t n_rows, int blocks_per_task, DecAcc* d_partials, DecAcc* d_acc,
+                           uint32_t* d_hll_regs, hipStream_t stream);
+hipError_t launch_init_dec_acc(DecAcc* d_acc, int n, hipStream_t stream);
+int scan_dec_blocks_per_cu();  // 0 = unknown
+// Decimal -> double of one column (scale s): values and an LSB-first validity bitmap at bit 0.
+hipError_t launch_cast_decimal(const DevColumn& src, int scale, int64_t n_rows, double* d_values, uint8_t* d_validity,
+                               hipStream_t stream);
 
 // ---------------------------------------------------------------- XXH64 (host + device)
 constexpr uint64_t kP1 = 0x9E3779B185EBCA87ull;

@@ -84,7 +84,9 @@ DQ_HD inline Val load_col(const DevColumn& c, int64_t row) {
     case DQ_T_INT64: v.i = static_cast<const int64_t*>(c.values)[row]; break;
     case DQ_T_FLOAT32: v.f = static_cast<const float*>(c.values)[row]; v.type = VT_FLT; break;
     case DQ_T_FLOAT64: v.f = static_cast<const double*>(c.values)[row]; v.type = VT_FLT; break;
-    default: v.null = 1; break;
+    default:  // (a decimal column: only its NULL flag is read, by IS [NOT] NULL)
+      if (DQ_T_BASE(c.type) != DQ_T_DECIMAL128) v.null = 1;
+      break;
   }
   return v;
 }

@@ -60,6 +60,10 @@ static dq_status schema_plan(const dq_schema_def* defs, int n_defs, const int32_
   s->types.assign(column_types, column_types + n_columns);
   for (int c = 0; c < n_columns; ++c)
     if (!valid_type(column_types[c])) return fail(DQ_ERR_INVALID, "dq_schema_create: unknown column type");
+  for (int c = 0; c < n_columns; ++c)  // (the gathers move 1- to 8-byte values: DESIGN.md §7)
+    if (is_decimal(column_types[c]))
+      return fail(DQ_ERR_UNSUPPORTED, "column " + std::to_string(c) + " is a " + decimal_name(column_types[c]) +
+                                          " column: decimal columns in the validator's input are not on the GPU path");
   s->cast_def.assign((size_t)n_columns, -1);
   s->defs.resize((size_t)n_defs);
   for (int i = 0; i < n_defs; ++i) {

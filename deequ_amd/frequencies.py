@@ -87,7 +87,9 @@ class FrequencyTable:
 
     def __init__(self, key_columns: Sequence[str], schema: Dict[str, str], histogram: bool = False,
                  device: Optional[int] = None, few_only: bool = False):
+        from .decimals import reject_decimal
         from .engine import current_device
+        reject_decimal(schema, key_columns, "Histogram" if histogram else "frequency group-by")
         self.key_columns = list(key_columns)
         self.schema = dict(schema)
         self.names = list(self.schema.keys())

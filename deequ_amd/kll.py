@@ -36,6 +36,14 @@ def check_parameters(sketchSize: int, shrinkingFactor: float) -> None:
     L.check(L.lib().dq_kll_supported(int(sketchSize), float(shrinkingFactor)))
 
 
+def check_column(schema: Dict[str, str], column: str) -> None:
+    """KLLRunner.scala:135-144 matches the column's type after isNumeric passed: a DecimalType column
+    reaches `case _ => throw new IllegalArgumentException(s"Cannot handle ${...dataType}")`."""
+    if L.is_decimal(schema.get(column)):
+        from .decimals import spark_type_name
+        raise ValueError("Cannot handle %s" % spark_type_name(schema[column]))
+
+
 class KLLSketcher:
     """Owns a dq_kll for (column, sketchSize, shrinkingFactor) triples over a fixed schema."""
 
@@ -103,6 +111,7 @@ def compute_kll_states(data, analyzers: Sequence, slab_rows: Optional[int] = Non
                                  "across ranks")
     keys, index = [], {}
     for a in analyzers:
+        check_column(data.schema, a.column)
         key = (a.column, a.sketchSize, a.shrinkingFactor)
         if key not in index:
             index[key] = len(keys)

@@ -308,6 +308,8 @@ class _Compiler:
         t = node[0]
         if t == "col":
             dtype = self.column(node[1])[1]
+            if L.is_decimal(dtype):
+                return "dec"
             return ("int" if dtype in _INTEGRAL else "f32" if dtype == "float32" else
                     "f64" if dtype == "float64" else "bool" if dtype == "bool" else "str")
         if t == "cast":
@@ -374,6 +376,8 @@ class _Compiler:
             idx, dtype = self.column(node[1])
             if dtype == "string" and target != "str":
                 raise UnsupportedPredicate("string column %s in a numeric context" % node[1])
+            if L.is_decimal(dtype):  # a decimal column's value: only IS [NOT] NULL takes it (emit_bool)
+                raise UnsupportedPredicate("decimal-typed expression")
             self.emit(L.DQ_P_COLUMN, idx)
             if target == "f32" and dtype in _INTEGRAL | {"bool"}:
                 self.emit(L.DQ_P_CAST, L.TYPE_CODES["float32"])
@@ -565,7 +569,9 @@ class _Compiler:
             self.emit(L.DQ_P_NOT)
         elif t in ("isnull", "isnotnull"):
             vt = self.vtype(node[1])
-            if node[1][0] in ("col", "lit", "coalesce", "cast"):
+            if node[1][0] == "col" and L.is_decimal(self.column(node[1][1])[1]):
+                self.emit(L.DQ_P_COLUMN, self.column(node[1][1])[0])  # the validity bit is all it reads
+            elif node[1][0] in ("col", "lit", "coalesce", "cast"):
                 self.emit_value(node[1], vt if vt in ("dbl", "str") else "int")
             else:
                 self.emit_bool(node[1])

@@ -138,7 +138,7 @@ def _known_type(dtype: str) -> int:
     reference's match and maps to Unknown."""
     if dtype in ("int16", "int32", "int64"):
         return DataTypeInstances.Integral
-    if dtype in ("float32", "float64"):
+    if dtype in ("float32", "float64") or L.is_decimal(dtype):  # DecimalType: Fractional (:410)
         return DataTypeInstances.Fractional
     if dtype == "bool":
         return DataTypeInstances.Boolean

@@ -81,6 +81,9 @@ def compute_quantile_states(data, analyzers: Sequence) -> Dict[object, ApproxQua
     if is_sharded(data):
         raise L.UnsupportedOnGpu(L.DQ_ERR_UNSUPPORTED, "ApproxQuantile over a ShardedTable: the ranks' target "
                                  "ranks are not gathered across ranks")
+    # a decimal column is cast to double first, as Spark casts the digest's input (decimals.py)
+    from .decimals import float64_view
+    data = float64_view(data, [a.column for a in analyzers])
     keys, index = [], {}
     for a in analyzers:
         key = (a.column, float(a.relativeError))

@@ -159,6 +159,9 @@ class AnalysisRunner:
         # would leave an ineligible analyzer on Spark; here it becomes a failure metric)
         eligible = []
         for a in shareable:
+            if a.castsDecimals(data.schema):  # Correlation of a decimal column: its own scan over the cast
+                results[a] = a.calculate(data, aggregateWith, saveStatesWith)
+                continue
             try:
                 op_supported(op_spec_for(a, data.schema), data.schema)
                 eligible.append(a)
@@ -192,11 +195,12 @@ class AnalysisRunner:
         """KLLRunner.computeKLLSketchesInExtraPass (KLLRunner.scala:89-122): one sketching pass for
         every KLL analyzer, then calculateMetric per analyzer.  Parameters the GPU sketcher declines
         fail their analyzer alone; an error of the pass fails them all."""
-        from .kll import check_parameters, compute_kll_states
+        from .kll import check_column, check_parameters, compute_kll_states
         results = OrderedDict()
         usable = []
         for a in analyzers:
             try:
+                check_column(data.schema, a.column)
                 check_parameters(a.sketchSize, a.shrinkingFactor)
                 usable.append(a)
             except Exception as e:  # noqa: BLE001

@@ -155,6 +155,8 @@ def check_schema(schema: RowLevelSchema, table_schema: Dict[str, str]) -> None:
     """The plan-time checks, without a device: ValueError for what Spark rejects, UnsupportedOnGpu
     (the message names the definition) for what the GPU declines."""
     _check_arguments(schema, list(table_schema.keys()))
+    from .decimals import reject_decimal
+    reject_decimal(table_schema, table_schema.keys(), "RowLevelSchemaValidator input")
     arr, n, types, _keep = _abi_definitions(schema, table_schema)
     L.check(L.lib().dq_schema_supported(arr, n, types, len(table_schema)))
 
@@ -167,6 +169,8 @@ class _Validator:
         self.ctx = L.Context.get(device)
         self.names = list(table_schema.keys())
         self.defs = list(schema.columnDefinitions)
+        from .decimals import reject_decimal
+        reject_decimal(table_schema, table_schema.keys(), "RowLevelSchemaValidator input")
         arr, n, types, self._keep = _abi_definitions(schema, table_schema)
         h = ctypes.c_void_p()
         L.check(L.lib().dq_schema_create(self.ctx.handle, arr, n, types, len(self.names), ctypes.byref(h)))

@@ -20,7 +20,30 @@ from . import _lib as L
 DTYPES = ("bool", "int8", "int16", "int32", "int64", "float32", "float64", "string")
 _NP = {"int8": np.int8, "int16": np.int16, "int32": np.int32, "int64": np.int64,
        "float32": np.float32, "float64": np.float64}
-NUMERIC = ("int8", "int16", "int32", "int64", "float32", "float64")
+# (also every "decimal(p,s)": 16 little-endian bytes per row, the two's-complement unscaled value,
+# held as an (n, 2) uint64 array -- Arrow decimal128)
+NUMERIC = L.NumericTypes(("int8", "int16", "int32", "int64", "float32", "float64"))
+
+
+def _unscaled(value, precision: int, scale: int) -> int:
+    """The unscaled integer of `value` (decimal.Decimal or int) at (precision, scale); ValueError
+    when the value does not fit exactly."""
+    import decimal
+    if isinstance(value, bool) or not isinstance(value, (int, decimal.Decimal)):
+        raise ValueError("a decimal column takes decimal.Decimal, int or None, not %r" % (value,))
+    d = decimal.Decimal(value)
+    if not d.is_finite():
+        raise ValueError("%r is not a finite decimal" % (value,))
+    with decimal.localcontext() as ctx:
+        ctx.prec = 100
+        u = d.scaleb(scale)
+        if u != u.to_integral_value():
+            raise ValueError("%r does not fit decimal(%d,%d) exactly: more than %d fractional digits"
+                             % (value, precision, scale, scale))
+        u = int(u)
+    if abs(u) >= 10 ** precision:
+        raise ValueError("%r does not fit decimal(%d,%d): more than %d digits" % (value, precision, scale, precision))
+    return u
 
 
 def pack_validity(valid: Optional[np.ndarray]) -> Optional[np.ndarray]:
@@ -37,7 +60,7 @@ class Column:
 
     def __init__(self, dtype: str, length: int, values, validity=None, offsets=None,
                  offset: int = 0, device: bool = False):
-        if dtype not in DTYPES:
+        if dtype not in DTYPES and not L.is_decimal(dtype):
             raise ValueError("unsupported column type %r" % dtype)
         self.dtype = dtype
         self.length = int(length)
@@ -57,6 +80,10 @@ class Column:
         if dtype == "bool":
             bits = np.packbits(values.astype(bool), bitorder="little")
             return Column("bool", len(values), bits, pack_validity(valid))
+        if L.is_decimal(dtype):  # the two 64-bit words of every row's 128-bit unscaled value
+            if values.dtype != np.uint64 or values.ndim != 2 or values.shape[1] != 2:
+                raise ValueError("a %s column takes an (n, 2) uint64 array" % dtype)
+            return Column(dtype, len(values), values, pack_validity(valid))
         return Column(dtype, len(values), values.astype(_NP[dtype], copy=False), pack_validity(valid))
 
     @staticmethod
@@ -68,14 +95,24 @@ class Column:
             np.cumsum([len(d) for d in data], out=offs[1:])
             buf = np.frombuffer(b"".join(data) + b"\0" * 8, dtype=np.uint8)
             return Column("string", len(values), buf, pack_validity(valid), offsets=offs)
+        ps = L.decimal_params(dtype)
+        if ps is not None:
+            words = np.zeros((len(values), 2), dtype=np.uint64)
+            for i, v in enumerate(values):
+                if v is not None:
+                    u = _unscaled(v, *ps) & ((1 << 128) - 1)
+                    words[i, 0] = u & 0xFFFFFFFFFFFFFFFF
+                    words[i, 1] = u >> 64
+            return Column(dtype, len(values), words, pack_validity(valid))
         fill = False if dtype == "bool" else 0
         arr = np.array([v if v is not None else fill for v in values],
                        dtype=bool if dtype == "bool" else _NP[dtype])
         return Column.from_numpy(arr, valid, dtype)
 
     @staticmethod
-    def from_arrow(arr) -> "Column":
-        """pyarrow.Array (single chunk) -> Column, zero-copy on the host."""
+    def from_arrow(arr, name: Optional[str] = None) -> "Column":
+        """pyarrow.Array (single chunk) -> Column, zero-copy on the host (`name`: the column's, for
+        error messages)."""
         import pyarrow as pa
         t = arr.type
         if pa.types.is_large_string(t):
@@ -84,6 +121,12 @@ class Column:
         kind = {pa.bool_(): "bool", pa.int8(): "int8", pa.int16(): "int16", pa.int32(): "int32",
                 pa.int64(): "int64", pa.float32(): "float32", pa.float64(): "float64",
                 pa.string(): "string"}.get(t)
+        if kind is None and pa.types.is_decimal128(t) and L.is_decimal("decimal(%d,%d)" % (t.precision, t.scale)):
+            kind = "decimal(%d,%d)" % (t.precision, t.scale)
+        if kind is None and pa.types.is_decimal(t):  # another width than 128, a negative scale
+            raise L.UnsupportedOnGpu(L.DQ_ERR_UNSUPPORTED, "%sArrow type %s is not on the GPU path (decimal columns "
+                                     "are decimal128 with a scale of 0..precision)"
+                                     % ("column %s: " % name if name else "", t))
         if kind is None:
             raise TypeError("unsupported arrow type %s" % t)
         bufs = arr.buffers()
@@ -96,6 +139,9 @@ class Column:
             return Column(kind, len(arr), data, validity, offsets=offs, offset=arr.offset)
         if kind == "bool":
             return Column(kind, len(arr), np.frombuffer(bufs[1], dtype=np.uint8), validity, offset=arr.offset)
+        if L.is_decimal(kind):
+            return Column(kind, len(arr), np.frombuffer(bufs[1], dtype=np.uint64).reshape(-1, 2), validity,
+                          offset=arr.offset)
         return Column(kind, len(arr), np.frombuffer(bufs[1], dtype=_NP[kind]), validity, offset=arr.offset)
 
     # ---------------------------------------------------------------- device residency
@@ -109,7 +155,10 @@ class Column:
         def up(a):
             if a is None:
                 return None
-            return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+            a = np.ascontiguousarray(a)
+            if a.dtype == np.uint64:  # (a decimal column's words: torch moves them as int64 bits)
+                a = a.view(np.int64)
+            return torch.from_numpy(a).to(dev)
         return Column(self.dtype, self.length, up(self.values), up(self.validity), up(self.offsets),
                       self.offset, device=True)
 
@@ -152,6 +201,10 @@ class Column:
             bits = np.unpackbits(np.asarray(vals, dtype=np.uint8), bitorder="little")
             bits = bits[self.offset:self.offset + self.length].astype(bool)
             return [bool(b) if ok else None for b, ok in zip(bits, valid)]
+        if L.is_decimal(self.dtype):  # the unscaled integers
+            w = np.asarray(vals).view(np.uint64).reshape(-1, 2)[self.offset:self.offset + self.length].tolist()
+            ints = [(lo | (hi << 64)) - ((hi >> 63) << 128) for lo, hi in w]
+            return [x if ok else None for x, ok in zip(ints, valid)]
         arr = np.asarray(vals)[self.offset:self.offset + self.length]
         return [x if ok else None for x, ok in zip(arr.tolist(), valid)]
 
@@ -193,7 +246,7 @@ class Table:
                     col = col.combine_chunks() if hasattr(col, "combine_chunks") else col.chunk(0)
                 else:
                     col = col.chunk(0)
-            cols[name] = Column.from_arrow(col)
+            cols[name] = Column.from_arrow(col, name)
         return Table(cols)
 
     def to_device(self, device: int = 0) -> "Table":

@@ -59,18 +59,33 @@ typedef enum dq_type {
   DQ_T_INT64 = 5,    /*                                             (LongType)          */
   DQ_T_FLOAT32 = 6,  /*                                             (FloatType)         */
   DQ_T_FLOAT64 = 7,  /*                                             (DoubleType)        */
-  DQ_T_UTF8 = 8      /* int32 offsets + UTF-8 bytes                 (StringType)        */
+  DQ_T_UTF8 = 8,     /* int32 offsets + UTF-8 bytes                 (StringType)        */
+  DQ_T_DECIMAL128 = 9 /* Arrow decimal128: 16 little-endian bytes per row, the two's-complement
+                         unscaled value                              (DecimalType(p, s)) */
 } dq_type;
+
+/* A decimal column's type code carries its precision and scale in the same int32 that every
+ * *_create / dq_op_supported takes and dq_column.type holds: DQ_T_DECIMAL(p, s) with precision
+ * 1..38 and scale 0..p (anything else is DQ_ERR_INVALID).  The low byte is the dq_type.
+ * Decimal columns serve Completeness, Sum, Mean, Minimum, Maximum, StandardDeviation and
+ * ApproxCountDistinct (one fused pass, dq_scan_dec.hip), `IS [NOT] NULL` in predicates, and
+ * dq_cast_decimal; every other op, a decimal grouping column of dq_freq_create, a decimal column
+ * sketched by dq_kll_create / dq_aq_create and a decimal column among dq_schema_create's /
+ * dq_schema_supported's input columns are DQ_ERR_UNSUPPORTED. */
+#define DQ_T_DECIMAL(p, s) ((int32_t)(DQ_T_DECIMAL128 | ((p) << 8) | ((s) << 16)))
+#define DQ_T_BASE(t) ((int32_t)((t) & 0xff))
+#define DQ_T_PRECISION(t) ((int32_t)(((t) >> 8) & 0xff))
+#define DQ_T_SCALE(t) ((int32_t)(((t) >> 16) & 0xff))
 
 #define DQ_COL_DEVICE 0x1 /* validity/values/offsets are device pointers on ctx's GPU */
 
 typedef struct dq_column {
-  int32_t type;             /* dq_type                                                   */
+  int32_t type;             /* dq_type; DQ_T_DECIMAL(p, s) for a decimal column          */
   int32_t flags;            /* DQ_COL_*                                                  */
   int64_t length;           /* number of rows in this batch                             */
   int64_t offset;           /* Arrow slot offset of row 0 (elements; bits for bitmaps)  */
   const uint8_t* validity;  /* LSB-first bitmap, 1 = valid; NULL = no nulls             */
-  const void* values;       /* fixed-width values, bit-packed bools, or utf8 bytes      */
+  const void* values;       /* fixed-width values (decimal: 16 B each), bit-packed bools, or utf8 bytes */
   const int32_t* offsets;   /* utf8 only: length+1 offsets (from `offset`)              */
 } dq_column;
 
@@ -260,8 +275,10 @@ dq_status dq_plan_finish(dq_plan* plan, dq_state* out, int n_out);
 
 /* Status of op `op` after dq_plan_finish: DQ_OK, or an error the op alone failed with (the
  * per-analyzer scope of AnalysisRunner.scala:340-353: the JNI layer fails or reroutes that
- * analyzer only).  Every op this library plans evaluates exactly, so it reports DQ_OK today;
- * the entry point keeps the per-op scope in the ABI. */
+ * analyzer only).  DQ_ERR_UNSUPPORTED: the data made the op one the GPU does not answer (never an
+ * approximation) -- a string -> double cast off the exact path in its predicate, or Sum / Mean of a
+ * decimal(p, s) column whose sum of |x| reaches 10^min(38, p + 10): Spark 2.2's decimal sum may
+ * overflow there, depending on the row order (SPARK-28067). */
 dq_status dq_plan_op_status(dq_plan* plan, int op);
 
 /* ---------------------------------------------------------------- Arrow C Data Interface
@@ -276,7 +293,8 @@ dq_status dq_plan_op_status(dq_plan* plan, int op);
  * "c" int8, "s" int16, "i" int32, "l" int64, "f" float32, "g" float64, "u" utf8.  Offsets of
  * sliced arrays (struct offset + child offset) are honoured; a NULL validity buffer means no
  * NULLs.  Rejected with DQ_ERR_UNSUPPORTED (route the batch to Spark): dictionary-encoded,
- * nested, large_utf8 ("U"), decimal, temporal formats and struct-level NULL rows.  Malformed
+ * nested, large_utf8 ("U"), decimal ("d:..."; a decimal128 column is handed over as a dq_column of
+ * type DQ_T_DECIMAL(p, s) through dq_plan_consume instead), temporal formats and struct-level NULL rows.  Malformed
  * structs (released, buffer counts, children shorter than the batch) give DQ_ERR_INVALID.
  * The caller keeps ownership: release callbacks are never invoked by the library, and the
  * buffers must stay valid until the next call on the plan / table returns (host buffers) or
@@ -365,6 +383,15 @@ uint64_t dq_xxh64(const void* data, size_t len, uint64_t seed);
  * *n_unsupported is always set to 0 (kept for ABI stability: nothing is routed back). */
 dq_status dq_cast_utf8(dq_ctx* ctx, const dq_column* src, int64_t n_rows, int32_t to_type,
                        void* d_values, uint8_t* d_validity, int64_t* n_unsupported);
+
+/* Spark 2.2.2 Cast(DecimalType(p, s) -> DoubleType) of one decimal column: Decimal.toDouble =
+ * java.math.BigDecimal.doubleValue, the correctly rounded (ties to even) value of unscaled / 10^s.
+ * Writes n_rows doubles and a validity bitmap (LSB-first, bit 0 = row 0; the source's NULLs) into
+ * DEVICE buffers on ctx's GPU (values: 8 n_rows bytes; validity: ceil(n_rows / 8) bytes).
+ * StandardDeviation casts each row this way inside the decimal scan; Correlation and ApproxQuantile
+ * of a decimal column run their float64 paths over this materialised column. */
+dq_status dq_cast_decimal(dq_ctx* ctx, const dq_column* src, int64_t n_rows, double* d_values_f64,
+                          uint8_t* d_validity);
 
 /* dq_cast_utf8 of n columns of n_rows rows each in one call (castNumericStringColumns casts every
  * string column pass 1 typed numeric): column i (utf8) -> to_types[i] into d_values[i] /

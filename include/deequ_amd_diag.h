@@ -99,6 +99,16 @@ dq_status dq_diag_kll_sketch(const double* values, const uint8_t* valid, int64_t
 dq_status dq_diag_schema_cell(int32_t kind, const uint8_t* text, int64_t n, int32_t precision, int32_t scale,
                               int32_t* result, int64_t* value);
 
+/* Host build of the decimal -> double cast (deequ_amd/csrc/dq_decimal.h, the source the decimal
+ * scan and dq_cast_decimal run on the device): the unscaled value lo | hi << 64 (two's complement)
+ * at `scale` (0..38), as java.math.BigDecimal.doubleValue rounds it.  *tier = which path took it:
+ * 1 one fp64 divide, 2 Eisel-Lemire, 3 the exact long division. */
+dq_status dq_diag_decimal_to_double(uint64_t lo, int64_t hi, int32_t scale, double* out, int32_t* tier);
+
+/* Host build of the bytes the decimal scan hashes for a precision > 18 column
+ * (java.math.BigInteger.toByteArray of the unscaled value): out[0 .. *len), *len in 1..16. */
+dq_status dq_diag_decimal_bytes(uint64_t lo, int64_t hi, uint8_t* out, int32_t* len);
+
 #ifdef __cplusplus
 }
 #endif
