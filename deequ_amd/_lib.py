@@ -193,6 +193,7 @@ DIAG_SIGNATURES = {
                                     POINTER(c_int64)]),
     "dq_diag_decimal_to_double": (c_int, [c_uint64, c_int64, c_int32, POINTER(c_double), POINTER(c_int32)]),
     "dq_diag_decimal_bytes": (c_int, [c_uint64, c_int64, c_char_p, POINTER(c_int32)]),
+    "dq_diag_plan_groups": (c_int, [c_void_p, POINTER(c_int64), c_int32, POINTER(c_int32), POINTER(c_int64)]),
 }
 
 
@@ -342,6 +343,24 @@ def check(status: int):
         if status == DQ_ERR_UNSUPPORTED:
             raise UnsupportedOnGpu(status, msg)
         raise DeequAmdError(status, msg)
+
+
+PLAN_LAUNCHES = ("regex", "string_pass", "hll", "datatype", "strlen", "corr", "dec")
+
+
+def diag_plan_groups(plan_handle):
+    """dq_diag_plan_groups of a dq_plan: ([(kind, value type, np, tasks, blocks per task, resident
+    workgroups per CU)] per scan group, {launch name: blocks per task, "rows", "dec_per_cu",
+    "n_cu"}) of the plan's last consumed batch (tests assert the kernels and grids a plan ran)."""
+    n = ctypes.c_int32(0)
+    launches = (c_int64 * 10)()
+    check(lib().dq_diag_plan_groups(plan_handle, None, 0, ctypes.byref(n), launches))
+    groups = (c_int64 * (6 * max(1, n.value)))()
+    check(lib().dq_diag_plan_groups(plan_handle, groups, n.value, ctypes.byref(n), launches))
+    out = [tuple(groups[6 * g:6 * g + 6]) for g in range(n.value)]
+    info = dict(zip(PLAN_LAUNCHES, launches[:7]))
+    info.update(rows=launches[7], dec_per_cu=launches[8], n_cu=launches[9])
+    return out, info
 
 
 def device_count() -> int:

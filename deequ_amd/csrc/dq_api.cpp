@@ -845,6 +845,12 @@ struct dq_plan : Stager {
   int target_blocks = 2048;
   int n_cu = 0;          // compute units of the device (0 = unknown)
   int scan_rounds = 6;   // value-scan grids: whole rounds of resident workgroups (DQ_SCAN_ROUNDS)
+  int max_blocks = 0;    // test hook: cap on every launch's blocks per task (DQ_SCAN_MAX_BLOCKS; 0 = none)
+  // the last consumed batch's grids, for dq_diag_plan_groups (host bookkeeping only)
+  std::vector<int64_t> diag_group_bpt;
+  int64_t diag_launch_bpt[7] = {0, 0, 0, 0, 0, 0, 0};  // regex, string pass, hll, datatype, strlen, corr, dec
+  int64_t diag_rows = 0;
+  int64_t cap_blocks(int64_t bpt) const { return max_blocks > 0 ? std::min<int64_t>(bpt, max_blocks) : bpt; }
   // host batches: staging slot k % 2, filled on copy_stream while the previous batch scans
   uint64_t batch_seq = 0;
   hipEvent_t copy_done[2] = {nullptr, nullptr}, scan_done[2] = {nullptr, nullptr};
@@ -1312,6 +1318,7 @@ extern "C" dq_status dq_plan_create(dq_ctx* ctx, const dq_op* ops, int n_ops,
     plan->n_cu = prop.multiProcessorCount;
   }
   if (const char* r = std::getenv("DQ_SCAN_ROUNDS")) plan->scan_rounds = std::max(0, std::atoi(r));
+  if (const char* r = std::getenv("DQ_SCAN_MAX_BLOCKS")) plan->max_blocks = std::max(0, std::atoi(r));
   if ((s = dq_plan_reset(plan)) != DQ_OK) {
     delete plan;
     return s;
@@ -1322,6 +1329,29 @@ extern "C" dq_status dq_plan_create(dq_ctx* ctx, const dq_op* ops, int n_ops,
 
 extern "C" dq_status dq_plan_destroy(dq_plan* plan) {
   delete plan;
+  return DQ_OK;
+}
+
+extern "C" dq_status dq_diag_plan_groups(dq_plan* plan, int64_t* groups, int32_t capacity, int32_t* n_groups,
+                                         int64_t* launches) {
+  if (!plan || !n_groups || !launches || capacity < 0 || (capacity > 0 && !groups))
+    return fail(DQ_ERR_INVALID, "dq_diag_plan_groups: NULL argument");
+  *n_groups = (int32_t)plan->groups.size();
+  const bool ran = plan->diag_group_bpt.size() == plan->groups.size() && plan->diag_rows > 0;
+  for (size_t g = 0; g < plan->groups.size() && (int32_t)g < capacity; ++g) {
+    const ScanGroup& G = plan->groups[g];
+    int64_t* o = groups + 6 * g;
+    o[0] = G.kind;
+    o[1] = G.kind == 0 ? 0 : G.ptype;
+    o[2] = G.np;
+    o[3] = (int64_t)G.tasks.size();
+    o[4] = ran ? plan->diag_group_bpt[g] : 0;
+    o[5] = plan->group_per_cu.size() == plan->groups.size() ? plan->group_per_cu[g] : 0;
+  }
+  for (int k = 0; k < 7; ++k) launches[k] = ran ? plan->diag_launch_bpt[k] : 0;
+  launches[7] = ran ? plan->diag_rows : 0;
+  launches[8] = plan->dec_per_cu > 0 ? plan->dec_per_cu : 0;
+  launches[9] = plan->n_cu;
   return DQ_OK;
 }
 
@@ -1551,7 +1581,7 @@ extern "C" dq_status dq_plan_consume(dq_plan* plan, const dq_column* columns, in
       const int per_cu = plan->group_per_cu[g];
       if (per_cu > 0) bpt = std::max<int64_t>(1, (int64_t)plan->n_cu * per_cu * plan->scan_rounds / ng);
     }
-    bpt = std::max<int64_t>(1, std::min<int64_t>(bpt, chunks));
+    bpt = plan->cap_blocks(std::max<int64_t>(1, std::min<int64_t>(bpt, chunks)));
     // a block's rows are addressed by 32-bit buffer offsets: keep its span <= 2^27 rows
     bpt = std::max<int64_t>(bpt, (chunks + (((int64_t)1 << 27) / kScanRowAlign) - 1) /
                                      (((int64_t)1 << 27) / kScanRowAlign));
@@ -1561,6 +1591,9 @@ extern "C" dq_status dq_plan_consume(dq_plan* plan, const dq_column* columns, in
       h_ranges[plan->groups[g].tasks[i]] = PartRange{part_total + i * bpt, (int32_t)bpt, 0};
     part_total += bpt * ng;
   }
+  plan->diag_group_bpt = group_bpt;
+  for (int64_t& b : plan->diag_launch_bpt) b = 0;
+  plan->diag_rows = n_rows;
   if (n_scan > 0) DQ_TRY(plan->d_partials.ensure((size_t)part_total * sizeof(ScanAcc)));
 
   DQ_HIP(hipMemcpyAsync(plan->d_cols.ptr, h_cols, n_columns * sizeof(DevColumn), hipMemcpyHostToDevice, plan->stream));
@@ -1593,7 +1626,8 @@ extern "C" dq_status dq_plan_consume(dq_plan* plan, const dq_column* columns, in
   }
   if (n_rx > 0) {  // every PatternMatch of the plan in one launch
     int64_t bpt = std::max<int64_t>(1, plan->target_blocks / n_rx);
-    bpt = std::min<int64_t>(bpt, (n_rows + kBlock - 1) / kBlock);
+    bpt = plan->cap_blocks(std::min<int64_t>(bpt, (n_rows + kBlock - 1) / kBlock));
+    plan->diag_launch_bpt[0] = bpt;
     DQ_HIP(launch_regex(static_cast<const RegexTask*>(plan->d_rx.ptr), n_rx, d_cols, d_masks,
                         static_cast<const uint8_t*>(plan->d_rx_dfas.ptr), plan->regex_lds, n_rows, (int)bpt,
                         static_cast<unsigned long long*>(plan->d_rx_out.ptr), side ? plan->side_stream : plan->stream));
@@ -1602,7 +1636,8 @@ extern "C" dq_status dq_plan_consume(dq_plan* plan, const dq_column* columns, in
   if (n_str > 0) {
     hipStream_t ss = side ? plan->side_stream : plan->stream;
     int64_t bpt = std::max<int64_t>(1, plan->target_blocks / n_str);
-    bpt = std::min<int64_t>(bpt, chunks);
+    bpt = plan->cap_blocks(std::min<int64_t>(bpt, chunks));
+    plan->diag_launch_bpt[1] = bpt;
     DQ_HIP(launch_string_pass(static_cast<const StrTask*>(plan->d_str.ptr), n_str, d_cols, d_masks, n_rows, (int)bpt,
                               static_cast<uint32_t*>(plan->d_regs.ptr),
                               static_cast<unsigned long long*>(plan->d_dtype_counts.ptr), ss));
@@ -1629,28 +1664,32 @@ extern "C" dq_status dq_plan_consume(dq_plan* plan, const dq_column* columns, in
   const int n_hll = (int)plan->hll_launch.size();
   if (n_hll > 0) {
     int64_t bpt = std::max<int64_t>(1, plan->target_blocks / n_hll);
-    bpt = std::min<int64_t>(bpt, chunks);
+    bpt = plan->cap_blocks(std::min<int64_t>(bpt, chunks));
+    plan->diag_launch_bpt[2] = bpt;
     DQ_HIP(launch_hll(static_cast<const HllTask*>(plan->d_hll.ptr), n_hll, d_cols, d_masks, n_rows, (int)bpt,
                       static_cast<uint32_t*>(plan->d_regs.ptr), plan->stream));
   }
   const int n_dt = (int)plan->dtype_launch.size();
   if (n_dt > 0) {
     int64_t bpt = std::max<int64_t>(1, plan->target_blocks / n_dt);
-    bpt = std::min<int64_t>(bpt, (n_rows + kBlock - 1) / kBlock);
+    bpt = plan->cap_blocks(std::min<int64_t>(bpt, (n_rows + kBlock - 1) / kBlock));
+    plan->diag_launch_bpt[3] = bpt;
     DQ_HIP(launch_datatype(static_cast<const HllTask*>(plan->d_dtype.ptr), n_dt, d_cols, d_masks, n_rows, (int)bpt,
                            static_cast<unsigned long long*>(plan->d_dtype_counts.ptr), plan->stream));
   }
   const int n_len = (int)plan->len_tasks.size();
   if (n_len > 0) {
     int64_t bpt = std::max<int64_t>(1, plan->target_blocks / n_len);
-    bpt = std::min<int64_t>(bpt, (n_rows + kBlock - 1) / kBlock);
+    bpt = plan->cap_blocks(std::min<int64_t>(bpt, (n_rows + kBlock - 1) / kBlock));
+    plan->diag_launch_bpt[4] = bpt;
     DQ_HIP(launch_strlen(static_cast<const HllTask*>(plan->d_len.ptr), n_len, d_cols, d_masks, n_rows, (int)bpt,
                          static_cast<unsigned long long*>(plan->d_len_out.ptr), plan->stream));
   }
   const int n_corr = (int)plan->corr_tasks.size();
   if (n_corr > 0) {
     int64_t bpt = std::max<int64_t>(1, plan->target_blocks / n_corr);
-    bpt = std::min<int64_t>(bpt, (n_rows + kBlock - 1) / kBlock);
+    bpt = plan->cap_blocks(std::min<int64_t>(bpt, (n_rows + kBlock - 1) / kBlock));
+    plan->diag_launch_bpt[5] = bpt;
     DQ_TRY(plan->d_corr_part.ensure((size_t)n_corr * (size_t)bpt * sizeof(CorrAcc)));
     DQ_HIP(launch_corr(static_cast<const CorrTask*>(plan->d_corr.ptr), n_corr, d_cols, d_masks, n_rows, (int)bpt,
                        static_cast<CorrAcc*>(plan->d_corr_part.ptr), static_cast<CorrAcc*>(plan->d_corr_acc.ptr),
@@ -1662,10 +1701,11 @@ extern "C" dq_status dq_plan_consume(dq_plan* plan, const dq_column* columns, in
     int64_t bpt = std::max<int64_t>(1, plan->target_blocks / n_dec);
     if (plan->n_cu > 0 && plan->dec_per_cu > 0 && plan->scan_rounds > 0)
       bpt = std::max<int64_t>(1, (int64_t)plan->n_cu * plan->dec_per_cu * plan->scan_rounds / n_dec);
-    bpt = std::max<int64_t>(1, std::min<int64_t>(bpt, chunks));
+    bpt = plan->cap_blocks(std::max<int64_t>(1, std::min<int64_t>(bpt, chunks)));
     // a block's limb sums hold 2^31 rows: keep its span <= 2^27 rows like the other scans
     bpt = std::max<int64_t>(bpt, (chunks + (((int64_t)1 << 27) / kScanRowAlign) - 1) /
                                      (((int64_t)1 << 27) / kScanRowAlign));
+    plan->diag_launch_bpt[6] = bpt;
     DQ_TRY(plan->d_dec_part.ensure((size_t)n_dec * (size_t)bpt * sizeof(DecAcc)));
     DQ_HIP(launch_scan_dec(static_cast<const DecTask*>(plan->d_dec.ptr), n_dec, d_cols, d_masks, n_rows, (int)bpt,
                            static_cast<DecAcc*>(plan->d_dec_part.ptr), static_cast<DecAcc*>(plan->d_dec_acc.ptr),

@@ -109,6 +109,21 @@ dq_status dq_diag_decimal_to_double(uint64_t lo, int64_t hi, int32_t scale, doub
  * (java.math.BigInteger.toByteArray of the unscaled value): out[0 .. *len), *len in 1..16. */
 dq_status dq_diag_decimal_bytes(uint64_t lo, int64_t hi, uint8_t* out, int32_t* len);
 
+/* The grids dq_plan_consume gave the plan's last non-empty batch (host bookkeeping: no kernel, no
+ * device read), so that tests can assert which kernel specialisations a plan ran and how many
+ * rows each block walked.  *n_groups = the plan's scan groups (one launch each); for the first
+ * min(*n_groups, capacity) of them groups[6g + 0..5] = kind (0 dq_scan_bits_kernel, 1
+ * dq_scan_values_kernel, 2 dq_scan_fast_kernel), value type (DQ_T_*; 0 for kind 0), np (kind 1:
+ * the inline-predicate count 0..4 or 8, -1 = the EXT kernel; kind 2: the fast variant, predicate
+ * kind | 8 statistics | 16 HLL), tasks in the group, blocks per task, resident workgroups per CU
+ * the occupancy query gave (0 = not asked).  launches[0..6] = blocks per task of the regex, string
+ * pass, HLL, DataType, MinLength/MaxLength, Correlation and decimal launches (0 = not launched),
+ * launches[7] = the batch's rows, launches[8] = the decimal scan's resident workgroups per CU (0 =
+ * not asked), launches[9] = the device's compute units.  `launches` holds 10 values.  Before the
+ * first batch every blocks-per-task value is 0. */
+dq_status dq_diag_plan_groups(dq_plan* plan, int64_t* groups, int32_t capacity, int32_t* n_groups,
+                              int64_t* launches);
+
 #ifdef __cplusplus
 }
 #endif
