@@ -2203,9 +2203,26 @@ extern "C" dq_status dq_diag_regex_match(const uint8_t* pattern, int32_t pattern
                                          int32_t* matched, int32_t* n_states, int32_t* n_classes) {
   if ((!pattern && pattern_len > 0) || pattern_len < 0 || (!text && n > 0) || n < 0 || !matched)
     return fail(DQ_ERR_INVALID, "bad argument");
-  regex::Dfa dfa;
-  std::string err;
-  if (!regex::compile(pattern, pattern_len, &dfa, &err)) return fail(DQ_ERR_UNSUPPORTED, err);
+  // The tests walk many texts per pattern: the calling thread keeps its last pattern's outcome, so
+  // that a pattern is compiled once per run of calls and not once per text.
+  struct Last {
+    bool any = false, ok = false;
+    std::string pattern, err;
+    regex::Dfa dfa;
+  };
+  static thread_local Last last;
+  if (!last.any || last.pattern.size() != (size_t)pattern_len ||
+      (pattern_len > 0 && std::memcmp(last.pattern.data(), pattern, (size_t)pattern_len) != 0)) {
+    last.any = false;
+    last.pattern.clear();
+    if (pattern_len > 0) last.pattern.assign(reinterpret_cast<const char*>(pattern), (size_t)pattern_len);
+    last.dfa = regex::Dfa();
+    last.err.clear();
+    last.ok = regex::compile(pattern, pattern_len, &last.dfa, &last.err);
+    last.any = true;
+  }
+  if (!last.ok) return fail(DQ_ERR_UNSUPPORTED, last.err);
+  const regex::Dfa& dfa = last.dfa;
   struct Text {
     const uint8_t* p;
     uint32_t operator[](int64_t i) const { return p[i]; }

@@ -77,7 +77,8 @@ dq_status dq_diag_uuid_pack(const uint8_t* key, int32_t len, uint64_t* words, ui
  * creation does (DQ_ERR_UNSUPPORTED with the construct and its offset in dq_last_error for a
  * pattern outside the exact subset), then *matched = 1 when java.util.regex's Matcher.find() would
  * succeed on text[0 .. n) with a non-empty group 0, else 0.  *n_states / *n_classes = the search
- * DFA's table shape (the columns include the end-of-input one).  text may be NULL with n = 0. */
+ * DFA's table shape (the columns include the end-of-input one).  text may be NULL with n = 0.
+ * Each thread keeps the outcome of its last pattern: calls that repeat it do not compile again. */
 dq_status dq_diag_regex_match(const uint8_t* pattern, int32_t pattern_len, const uint8_t* text, int64_t n,
                               int32_t* matched, int32_t* n_states, int32_t* n_classes);
 

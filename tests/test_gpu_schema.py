@@ -26,6 +26,10 @@ DEFS = [
     {"kind": "int", "name": "i", "minValue": -1000, "maxValue": 100000},
     {"kind": "decimal", "name": "d", "precision": 10, "scale": 2},
 ]
+# DEFS with another `matches`: a search that may start and end anywhere in the cell, and an alternation of
+# an anchored branch with multi-byte classes (2-, 3- and 4-byte members, a Latin-1 and a CJK range)
+OTHER_PATTERNS = {"unanchored": r"[a-z]{3}[0-9]", "alternation": r"^[a-m][a-z]+[0-9]*$|[é日ñ😀€本][^a-z]|[à-ÿ一-鿿]$"}
+OTHER_DEFS = {k: [dict(DEFS[0], matches=p)] + DEFS[1:] for k, p in OTHER_PATTERNS.items()}
 
 
 def _pools():
@@ -116,10 +120,11 @@ def test_reference_case(gpu, case):
 
 
 # ---------------------------------------------------------------- random tables
-@pytest.mark.parametrize("n", [1, 63, 64, 65, 1000, 100003, 64 * SCAN_TILE + 1, 300000])
-def test_random_table(gpu, n):
+@pytest.mark.parametrize("n,defs", [pytest.param(n, DEFS, id=str(n)) for n in [1, 63, 64, 65, 1000, 100003, 64 * SCAN_TILE + 1, 300000]] +
+                         [pytest.param(n, OTHER_DEFS[k], id="%d-%s" % (n, k)) for k in OTHER_DEFS for n in [64, 1000, 100003]])
+def test_random_table(gpu, n, defs):
     cols = random_columns(n, 1000 + n)
-    res, m = check(cols, DEFS, device=n % 2 == 1)
+    res, m = check(cols, defs, device=n % 2 == 1)
     if n >= 1000:  # every verdict occurs, and a good share of each output
         assert min(len(m.valid_idx), len(m.invalid_idx)) > n // 5 and len(m.null_idx) > n // 100
 
