@@ -32,6 +32,7 @@ DQ_P_CAST = 8  # arg = target dq_type (TYPE_CODES)
 DQ_P_EQ, DQ_P_NE, DQ_P_LT, DQ_P_LE, DQ_P_GT, DQ_P_GE, DQ_P_EQ_NULLSAFE = 10, 11, 12, 13, 14, 15, 16
 DQ_P_IS_NULL, DQ_P_IS_NOT_NULL = 20, 21
 DQ_P_AND, DQ_P_OR, DQ_P_NOT, DQ_P_TRUE, DQ_P_FALSE = 30, 31, 32, 33, 34
+DQ_P_LIKE, DQ_P_RLIKE = 40, 41  # Like / RLike(utf8 column, string literal)
 DQ_CMP_AS_INT64, DQ_CMP_AS_FLOAT64 = 0, 1
 
 DQ_HLL_NUM_WORDS = 52
@@ -187,6 +188,9 @@ DIAG_SIGNATURES = {
     "dq_diag_eval_predicate": (c_int, [POINTER(DqPredicate), POINTER(DqColumn), c_int, c_int64, c_void_p]),
     "dq_diag_regex_match": (c_int, [c_char_p, c_int32, c_char_p, c_int64, POINTER(c_int32), POINTER(c_int32),
                                     POINTER(c_int32)]),
+    "dq_diag_regex_match_mode": (c_int, [c_char_p, c_int32, c_int32, c_char_p, c_int64, POINTER(c_int32),
+                                         POINTER(c_int32), POINTER(c_int32), c_void_p, c_int64, POINTER(c_int64)]),
+    "dq_diag_plan_match_tasks": (c_int, [c_void_p, POINTER(c_int32), POINTER(c_int32)]),
     "dq_diag_kll_sketch": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_double, c_int64, c_void_p, c_int64,
                                    POINTER(c_int64)]),
     "dq_diag_schema_cell": (c_int, [c_int32, c_char_p, c_int64, c_int32, c_int32, POINTER(c_int32),
@@ -361,6 +365,31 @@ def diag_plan_groups(plan_handle):
     info = dict(zip(PLAN_LAUNCHES, launches[:7]))
     info.update(rows=launches[7], dec_per_cu=launches[8], n_cu=launches[9])
     return out, info
+
+
+REGEX_MODES = {"find_non_empty": 0, "find": 1, "full": 2}
+
+
+def diag_regex_match(pattern: bytes, text: bytes, mode: str = "find_non_empty", want_image: bool = False):
+    """dq_diag_regex_match_mode: (matched, DFA states, DFA columns[, the DFA image]) of the host
+    build of the regex / LIKE compiler and walker in one of REGEX_MODES ("full": `pattern` is a SQL
+    LIKE pattern).  Raises UnsupportedOnGpu with the compiler's message for a declined pattern."""
+    m, ns, nc = c_int32(0), c_int32(0), c_int32(0)
+    size = c_int64(0)
+    args = (pattern, len(pattern), REGEX_MODES[mode], text, len(text), ctypes.byref(m), ctypes.byref(ns), ctypes.byref(nc))
+    check(lib().dq_diag_regex_match_mode(*args, None, 0, ctypes.byref(size)))
+    if not want_image:
+        return m.value, ns.value, nc.value
+    buf = ctypes.create_string_buffer(size.value)
+    check(lib().dq_diag_regex_match_mode(*args, buf, size.value, ctypes.byref(size)))
+    return m.value, ns.value, nc.value, buf.raw
+
+
+def diag_plan_match_tasks(plan_handle):
+    """(LIKE / RLIKE match tasks, distinct DFA images) of a dq_plan."""
+    t, i = c_int32(0), c_int32(0)
+    check(lib().dq_diag_plan_match_tasks(plan_handle, ctypes.byref(t), ctypes.byref(i)))
+    return t.value, i.value
 
 
 def device_count() -> int:

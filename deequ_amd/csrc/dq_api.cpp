@@ -13,6 +13,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <limits>
 #include <memory>
 #include <mutex>
@@ -426,12 +427,55 @@ extern "C" dq_status dq_ctx_destroy(dq_ctx* ctx) {
 // V_DEC is a decimal column's value: only IS [NOT] NULL takes it.
 enum VT { V_INT = 0, V_FLT = 1, V_BOOL = 2, V_STR = 3, V_F32 = 4, V_NULL = 5, V_DEC = 6 };
 
+// A LIKE / RLIKE of a program: its kPredMatch instruction carries the index into Program::matches
+// until plan creation gives it the plan-wide match task.
+struct ProgramMatch {
+  int column;
+  std::string key;  // mode byte + pattern bytes: names the DFA image
+  std::shared_ptr<const std::vector<uint8_t>> image;
+};
+
 struct Program {
   std::vector<PredInsn> code;
   std::vector<int> columns;  // referenced batch columns (sorted, unique)
   std::string pool;          // string literals (DQ_P_LIT_STRING), offsets relative to this
   std::string key;           // byte image for de-duplication
+  std::vector<ProgramMatch> matches;
 };
+
+// The DFA image of (mode, pattern), compiled once: validation runs for dq_op_supported, for the
+// plan's checks and again when the plan is built, and a plan repeats patterns across its ops.
+// nullptr = declined (*err says why).
+static std::shared_ptr<const std::vector<uint8_t>> match_image(regex::Mode mode, const uint8_t* pat, int32_t len,
+                                                               std::string* err) {
+  struct Entry {
+    std::string key, err;
+    std::shared_ptr<const std::vector<uint8_t>> image;
+  };
+  static std::mutex mu;
+  static std::deque<Entry> cache;  // most recent first
+  std::string key(1, (char)mode);
+  if (len > 0) key.append(reinterpret_cast<const char*>(pat), (size_t)len);
+  {
+    std::lock_guard<std::mutex> lock(mu);
+    for (const Entry& e : cache)
+      if (e.key == key) {
+        if (!e.image) *err = e.err;
+        return e.image;
+      }
+  }
+  Entry e;
+  e.key = key;
+  regex::Dfa dfa;
+  const bool ok = mode == regex::kFull ? regex::compile_like(pat, len, &dfa, &e.err)
+                                       : regex::compile_mode(pat, len, mode, &dfa, &e.err);
+  if (ok) e.image = std::make_shared<const std::vector<uint8_t>>(dfa.image());
+  else *err = e.err;
+  std::lock_guard<std::mutex> lock(mu);
+  cache.push_front(e);
+  if (cache.size() > 64) cache.pop_back();
+  return e.image;
+}
 
 static bool vt_fractional(int t) { return t == V_FLT || t == V_F32; }
 
@@ -552,6 +596,32 @@ static dq_status validate_predicate(const dq_predicate& p, const int32_t* types,
         st.push_back(V_BOOL);
         break;
       }
+      case DQ_P_LIKE: case DQ_P_RLIKE: {  // Like / RLike(utf8 column, string literal) and nothing else
+        const char* name = in.opcode == DQ_P_LIKE ? "LIKE" : "RLIKE";
+        if (st.size() < 2) return fail(DQ_ERR_INVALID, "predicate stack underflow");
+        const size_t nc = prog.code.size();
+        const bool shape = nc >= 2 && prog.code[nc - 2].opcode == DQ_P_COLUMN && prog.code[nc - 1].opcode == DQ_P_LIT_STRING &&
+                           types[prog.code[nc - 2].arg] == DQ_T_UTF8;
+        if (!shape)
+          return fail(DQ_ERR_UNSUPPORTED, std::string(name) + " takes a string column on the left and one string "
+                      "literal on the right on the GPU path");
+        const PredInsn lit = prog.code[nc - 1];
+        const int column = prog.code[nc - 2].arg;
+        std::string err;
+        ProgramMatch m;
+        m.column = column;
+        const uint8_t* text = lit.arg > 0 ? p.strings + lit.i64 : nullptr;  // (an empty literal may come without a pool)
+        m.image = match_image(in.opcode == DQ_P_LIKE ? regex::kFull : regex::kFind, text, lit.arg, &err);
+        if (!m.image) return fail(DQ_ERR_UNSUPPORTED, err);
+        m.key.assign(1, in.opcode == DQ_P_LIKE ? 'L' : 'R');
+        if (lit.arg > 0) m.key.append(reinterpret_cast<const char*>(p.strings + lit.i64), (size_t)lit.arg);
+        prog.code.resize(nc - 2);
+        st.pop_back();
+        st.back() = V_BOOL;
+        pi = PredInsn{kPredMatch, column, (int64_t)prog.matches.size(), 0.0};
+        prog.matches.push_back(std::move(m));
+        break;
+      }
       default:
         return fail(DQ_ERR_UNSUPPORTED, "unknown predicate opcode " + std::to_string(in.opcode));
     }
@@ -566,6 +636,10 @@ static dq_status validate_predicate(const dq_predicate& p, const int32_t* types,
   if (p.strings && p.strings_len > 0) prog.pool.assign(reinterpret_cast<const char*>(p.strings), p.strings_len);
   prog.key.assign(reinterpret_cast<const char*>(prog.code.data()), prog.code.size() * sizeof(PredInsn));
   prog.key += prog.pool;
+  for (const ProgramMatch& m : prog.matches) {  // (the instruction names the column, this the pattern)
+    prog.key += std::to_string(m.key.size()) + ":";
+    prog.key += m.key;
+  }
   if (out) *out = std::move(prog);
   return DQ_OK;
 }
@@ -825,6 +899,12 @@ struct dq_plan : Stager {
   std::vector<uint32_t> regex_offsets;  // of each pattern's image in regex_images
   std::vector<uint8_t> regex_images;
   uint32_t regex_lds = 0;  // bytes of the largest staged image (byte map + table)
+  // LIKE / RLIKE of the predicate programs: distinct {column, DFA}; their images follow
+  // PatternMatch's in regex_images, one per distinct (mode, pattern)
+  std::vector<MatchTask> match_tasks;
+  std::vector<std::string> match_keys;
+  std::vector<uint32_t> match_offsets;  // of each key's image in regex_images
+  uint32_t match_lds = 0;
   std::vector<Program> programs;  // generic predicate programs -> batch masks
   // device state
   std::vector<dq_status> op_status;  // per op, after dq_plan_finish
@@ -832,7 +912,7 @@ struct dq_plan : Stager {
   bool pred_cast = false;  // a predicate program casts a string to double (its own kernel: the parser's scratch)
   DevBuf d_tasks, d_groups, d_ranges, d_hll, d_progs, d_insns, d_pool, d_acc, d_partials, d_regs,
       d_cols, d_masks, d_mask_words, d_dtype, d_dtype_counts, d_len, d_len_out, d_corr, d_corr_part, d_corr_acc, d_str, d_rx, d_rx_dfas, d_rx_out,
-      d_dec, d_dec_acc, d_dec_part;
+      d_dec, d_dec_acc, d_dec_part, d_match, d_match_words;
   int64_t mask_words = 0;
   // pinned descriptor staging (DevColumn + DevMask arrays) guarded by an event
   void* h_desc = nullptr;
@@ -1233,6 +1313,28 @@ extern "C" dq_status dq_plan_create(dq_ctx* ctx, const dq_op* ops, int n_ops,
     for (PredInsn in : p.code) {
       if (in.opcode == DQ_P_LIT_STRING) in.i64 += (int64_t)pool.size();  // plan-wide pool offset
       if (in.opcode == DQ_P_CAST_DOUBLE) plan->pred_cast = true;
+      if (in.opcode == kPredMatch) {  // the plan's task for this (column, pattern, mode)
+        const ProgramMatch& m = p.matches[(size_t)in.i64];
+        int d = -1;
+        for (size_t k = 0; k < plan->match_keys.size(); ++k)
+          if (plan->match_keys[k] == m.key) d = (int)k;
+        if (d < 0) {
+          d = (int)plan->match_keys.size();
+          plan->match_keys.push_back(m.key);
+          plan->match_offsets.push_back((uint32_t)plan->regex_images.size());
+          plan->regex_images.insert(plan->regex_images.end(), m.image->begin(), m.image->end());
+          plan->match_lds = std::max(plan->match_lds, (uint32_t)m.image->size() - regex::kRegexHeaderBytes);
+        }
+        const uint32_t off = plan->match_offsets[d];
+        int t = -1;
+        for (size_t k = 0; k < plan->match_tasks.size(); ++k)
+          if (plan->match_tasks[k].column == m.column && plan->match_tasks[k].dfa_off == off) t = (int)k;
+        if (t < 0) {
+          plan->match_tasks.push_back(MatchTask{m.column, off});
+          t = (int)plan->match_tasks.size() - 1;
+        }
+        in.i64 = t;
+      }
       insns.push_back(in);
     }
     pool += p.pool;
@@ -1275,6 +1377,7 @@ extern "C" dq_status dq_plan_create(dq_ctx* ctx, const dq_op* ops, int n_ops,
       (s = plan->d_corr_acc.ensure(std::max<size_t>(1, plan->corr_tasks.size()) * sizeof(CorrAcc))) != DQ_OK ||
       (s = upload(plan->d_rx, plan->regex_tasks.data(), plan->regex_tasks.size() * sizeof(RegexTask))) != DQ_OK ||
       (s = upload(plan->d_rx_dfas, plan->regex_images.data(), plan->regex_images.size())) != DQ_OK ||
+      (s = upload(plan->d_match, plan->match_tasks.data(), plan->match_tasks.size() * sizeof(MatchTask))) != DQ_OK ||
       (s = plan->d_rx_out.ensure(std::max<size_t>(1, plan->regex_tasks.size()) * 2 * sizeof(uint64_t))) != DQ_OK ||
       (s = upload(plan->d_dec, plan->dec_tasks.data(), plan->dec_tasks.size() * sizeof(DecTask))) != DQ_OK ||
       (s = plan->d_dec_acc.ensure(std::max<size_t>(1, plan->dec_tasks.size()) * sizeof(DecAcc))) != DQ_OK ||
@@ -1606,12 +1709,19 @@ extern "C" dq_status dq_plan_consume(dq_plan* plan, const dq_column* columns, in
 
   const DevColumn* d_cols = static_cast<const DevColumn*>(plan->d_cols.ptr);
   const DevMask* d_masks = static_cast<const DevMask*>(plan->d_masks.ptr);
+  const int n_match = (int)plan->match_tasks.size();
+  if (n_match > 0) {  // every LIKE / RLIKE of the plan's programs in one launch, ahead of the interpreter
+    DQ_TRY(plan->d_match_words.ensure((size_t)plan->mask_words * n_match * sizeof(uint64_t)));
+    DQ_HIP(launch_match_mask(static_cast<const MatchTask*>(plan->d_match.ptr), n_match, d_cols,
+                             static_cast<const uint8_t*>(plan->d_rx_dfas.ptr), plan->match_lds, n_rows,
+                             static_cast<uint64_t*>(plan->d_match_words.ptr), plan->mask_words, plan->stream));
+  }
   if (n_progs > 0)
     DQ_HIP(launch_predicates(static_cast<const PredProgram*>(plan->d_progs.ptr), n_progs,
                              static_cast<const PredInsn*>(plan->d_insns.ptr),
                              static_cast<const uint8_t*>(plan->d_pool.ptr), d_cols, n_rows,
                              static_cast<uint64_t*>(plan->d_mask_words.ptr), plan->mask_words, plan->pred_cast,
-                             plan->stream));
+                             plan->stream, static_cast<const uint64_t*>(plan->d_match_words.ptr)));
 
   const int n_str = (int)plan->str_tasks.size();
   const int n_rx = (int)plan->regex_tasks.size();
@@ -2233,6 +2343,57 @@ extern "C" dq_status dq_diag_regex_match(const uint8_t* pattern, int32_t pattern
   return DQ_OK;
 }
 
+// The same in any of the compiler's modes (0 find-non-empty, 1 find, 2 full = a LIKE pattern).
+extern "C" dq_status dq_diag_regex_match_mode(const uint8_t* pattern, int32_t pattern_len, int32_t mode,
+                                              const uint8_t* text, int64_t n, int32_t* matched, int32_t* n_states,
+                                              int32_t* n_classes, uint8_t* image, int64_t image_capacity,
+                                              int64_t* image_len) {
+  if ((!pattern && pattern_len > 0) || pattern_len < 0 || (!text && n > 0) || n < 0 || !matched || mode < 0 || mode > 2 ||
+      image_capacity < 0 || (!image && image_capacity > 0))
+    return fail(DQ_ERR_INVALID, "bad argument");
+  struct Last {
+    bool any = false, ok = false;
+    int32_t mode = 0;
+    std::string pattern, err;
+    regex::Dfa dfa;
+  };
+  static thread_local Last last;
+  if (!last.any || last.mode != mode || last.pattern.size() != (size_t)pattern_len ||
+      (pattern_len > 0 && std::memcmp(last.pattern.data(), pattern, (size_t)pattern_len) != 0)) {
+    last.any = false;
+    last.mode = mode;
+    last.pattern.clear();
+    if (pattern_len > 0) last.pattern.assign(reinterpret_cast<const char*>(pattern), (size_t)pattern_len);
+    last.dfa = regex::Dfa();
+    last.err.clear();
+    last.ok = mode == regex::kFull ? regex::compile_like(pattern, pattern_len, &last.dfa, &last.err)
+                                   : regex::compile_mode(pattern, pattern_len, (regex::Mode)mode, &last.dfa, &last.err);
+    last.any = true;
+  }
+  if (!last.ok) return fail(DQ_ERR_UNSUPPORTED, last.err);
+  const regex::Dfa& dfa = last.dfa;
+  struct Text {
+    const uint8_t* p;
+    uint32_t operator[](int64_t i) const { return p[i]; }
+  };
+  *matched = regex::regex_walk(dfa.cmap, dfa.table.data(), dfa.n_cols, dfa.start_row, Text{text}, n) ? 1 : 0;
+  if (n_states) *n_states = (int32_t)dfa.n_states;
+  if (n_classes) *n_classes = (int32_t)dfa.n_cols;
+  if (image || image_len) {
+    const std::vector<uint8_t> img = dfa.image();
+    if (image_len) *image_len = (int64_t)img.size();
+    if (image && image_capacity >= (int64_t)img.size()) std::memcpy(image, img.data(), img.size());
+  }
+  return DQ_OK;
+}
+
+extern "C" dq_status dq_diag_plan_match_tasks(dq_plan* plan, int32_t* n_tasks, int32_t* n_images) {
+  if (!plan || !n_tasks || !n_images) return fail(DQ_ERR_INVALID, "bad argument");
+  *n_tasks = (int32_t)plan->match_tasks.size();
+  *n_images = (int32_t)plan->match_keys.size();
+  return DQ_OK;
+}
+
 // Host build of the predicate interpreter (dq_predeval.h, the same source dq_pred_kernel runs):
 // validates `p` against the columns' types exactly as plan creation does, then evaluates it row
 // by row over host columns.  out[r] = 0 FALSE, 1 TRUE, 2 NULL.
@@ -2252,9 +2413,17 @@ extern "C" dq_status dq_diag_eval_predicate(const dq_predicate* p, const dq_colu
   Program prog;
   DQ_TRY(validate_predicate(*p, types.data(), n_cols, &prog));
   const uint8_t* pool = reinterpret_cast<const uint8_t*>(prog.pool.data());
+  // LIKE / RLIKE: the program's own matches are the tasks, their images back to back
+  std::vector<uint8_t> images;
+  std::vector<uint32_t> offsets;
+  for (const ProgramMatch& m : prog.matches) {
+    offsets.push_back((uint32_t)images.size());
+    images.insert(images.end(), m.image->begin(), m.image->end());
+  }
+  const MatchSource ms{nullptr, 0, images.data(), offsets.data()};
   for (int64_t r = 0; r < n_rows; ++r) {
     bool t = false, nn = false;
-    pred::eval_program<true>(prog.code.data(), (int)prog.code.size(), pool, dc.data(), r, t, nn);
+    pred::eval_program<true>(prog.code.data(), (int)prog.code.size(), pool, dc.data(), r, t, nn, ms);
     out[r] = nn ? (t ? 1 : 0) : 2;
   }
   return DQ_OK;

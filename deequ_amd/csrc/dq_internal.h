@@ -137,6 +137,25 @@ struct RegexTask {
   int32_t pad;
 };
 
+// LIKE / RLIKE in a predicate (dq_regex.hip: dq_match_mask_kernel): one compiled pattern over one
+// string column; one bit per row (matched, 0 for a NULL row) in 64-bit words, LSB first, which the
+// predicate interpreter reads through kPredMatch.  The images lie next to PatternMatch's.
+struct MatchTask {
+  int32_t column;
+  uint32_t dfa_off;
+};
+// The validator's rewrite of the triple DQ_P_COLUMN, DQ_P_LIT_STRING, DQ_P_LIKE | DQ_P_RLIKE
+// (never in a caller's program): arg = the column, i64 = the match task.
+constexpr int32_t kPredMatch = 1000;
+// What the interpreter reads a match from: the device build the mask words of the batch, the host
+// build (dq_diag_eval_predicate) the images, which it walks over the row's bytes.
+struct MatchSource {
+  const uint64_t* words;     // device: task k's mask at words + k * words_per_mask
+  int64_t words_per_mask;
+  const uint8_t* images;     // host: task k's image at images + offsets[k]
+  const uint32_t* offsets;
+};
+
 // Correlation task (dq_pair.hip) and its running state CorrelationState(n, xAvg, yAvg, ck, xMk, yMk).
 struct CorrTask {
   int32_t x, y;
@@ -521,7 +540,13 @@ hipError_t launch_hll(const HllTask* d_tasks, int n_tasks, const DevColumn* d_co
                       uint32_t* d_registers, hipStream_t stream);
 hipError_t launch_predicates(const PredProgram* d_progs, int n_progs, const PredInsn* d_insns,
                              const uint8_t* d_pool, const DevColumn* d_cols, int64_t n_rows,
-                             uint64_t* d_mask_words, int64_t words_per_mask, bool with_cast, hipStream_t stream);
+                             uint64_t* d_mask_words, int64_t words_per_mask, bool with_cast, hipStream_t stream,
+                             const uint64_t* d_match_words = nullptr);
+// LIKE / RLIKE match masks (dq_regex.hip): task k's words at d_out + k * words_per_mask; lds_bytes
+// = the largest staged image of the launch.  Launched before launch_predicates on the same stream.
+hipError_t launch_match_mask(const MatchTask* d_tasks, int n_tasks, const DevColumn* d_cols, const uint8_t* d_dfas,
+                             uint32_t lds_bytes, int64_t n_rows, uint64_t* d_out, int64_t words_per_mask,
+                             hipStream_t stream);
 hipError_t launch_rebase_offsets(int32_t* d_offs, int64_t n, int32_t first, hipStream_t stream);
 hipError_t launch_realign_bitmap(const uint8_t* src, int64_t bit_offset, int64_t n_bits,
                                  uint8_t* dst, hipStream_t stream);

@@ -7,6 +7,8 @@
 // postfix interpreter (the plan's validated dq_pred_insn program).  Each wave evaluates 64
 // consecutive rows and writes two 64-bit ballot words: TRUE bits and NOT-NULL bits.  The scan
 // kernel then reads those masks (2 bits per row instead of the referenced columns' bytes).
+// A LIKE / RLIKE of a program is not walked here: dq_match_mask_kernel (dq_regex.hip) has written
+// one bit per row before this kernel starts, and the interpreter reads it (kPredMatch).
 // The interpreter itself (types, three-valued logic, Spark 2.2's casts) is dq_predeval.h, shared
 // with the host build the CPU tests check against the oracle.
 #include "dq_predeval.h"
@@ -19,18 +21,20 @@ __global__ __launch_bounds__(kBlock) void dq_pred_kernel(const PredProgram* __re
                                                          const uint8_t* __restrict__ pool,
                                                          const DevColumn* __restrict__ cols,
                                                          int64_t n_rows, uint64_t* out,
-                                                         int64_t words_per_mask) {
+                                                         int64_t words_per_mask,
+                                                         const uint64_t* __restrict__ match_words) {
   const PredProgram prog = progs[blockIdx.y];
   const PredInsn* code = insns + prog.first;
   const int lane = threadIdx.x & 63;
   const int64_t n_words = (n_rows + 63) >> 6;
   uint64_t* out_t = out + (int64_t)(2 * blockIdx.y) * words_per_mask;
   uint64_t* out_n = out_t + words_per_mask;
+  const MatchSource ms{match_words, words_per_mask, nullptr, nullptr};
   for (int64_t w = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); w < n_words;
        w += (int64_t)gridDim.x * (kBlock / 64)) {
     const int64_t row = (w << 6) + lane;
     bool t = false, nn = false;
-    if (row < n_rows) pred::eval_program<CAST>(code, prog.n, pool, cols, row, t, nn);
+    if (row < n_rows) pred::eval_program<CAST>(code, prog.n, pool, cols, row, t, nn, ms);
     const uint64_t bt = __ballot(t);
     const uint64_t bn = __ballot(nn);
     if (lane == 0) {
@@ -59,17 +63,18 @@ __global__ void dq_realign_kernel(const uint8_t* __restrict__ src, int64_t bit_o
 
 hipError_t launch_predicates(const PredProgram* d_progs, int n_progs, const PredInsn* d_insns,
                              const uint8_t* d_pool, const DevColumn* d_cols, int64_t n_rows,
-                             uint64_t* d_mask_words, int64_t words_per_mask, bool with_cast, hipStream_t stream) {
+                             uint64_t* d_mask_words, int64_t words_per_mask, bool with_cast, hipStream_t stream,
+                             const uint64_t* d_match_words) {
   if (n_progs <= 0 || n_rows <= 0) return hipSuccess;
   const int64_t n_words = (n_rows + 63) >> 6;
   int64_t blocks = (n_words + 3) / 4;
   if (blocks > 2048) blocks = 2048;
   if (with_cast)
     hipLaunchKernelGGL(dq_pred_kernel<true>, dim3((unsigned)blocks, n_progs), dim3(kBlock), 0, stream,
-                       d_progs, d_insns, d_pool, d_cols, n_rows, d_mask_words, words_per_mask);
+                       d_progs, d_insns, d_pool, d_cols, n_rows, d_mask_words, words_per_mask, d_match_words);
   else
     hipLaunchKernelGGL(dq_pred_kernel<false>, dim3((unsigned)blocks, n_progs), dim3(kBlock), 0, stream,
-                       d_progs, d_insns, d_pool, d_cols, n_rows, d_mask_words, words_per_mask);
+                       d_progs, d_insns, d_pool, d_cols, n_rows, d_mask_words, words_per_mask, d_match_words);
   return hipGetLastError();
 }
 

@@ -19,6 +19,7 @@
 
 #include "dq_internal.h"
 #include "dq_numparse.h"
+#include "dq_regex.h"
 
 namespace dq {
 namespace pred {
@@ -147,7 +148,7 @@ DQ_HD inline void cast_value(Val& a, int target) {
 // device); programs without one are compiled without the parser.
 template <bool CAST>
 DQ_HD inline void eval_program(const PredInsn* code, int n, const uint8_t* pool, const DevColumn* cols,
-                               int64_t row, bool& t, bool& nn) {
+                               int64_t row, bool& t, bool& nn, const MatchSource& ms) {
   Val st[kMaxStack];
   int sp = 0;
   for (int pc = 0; pc < n; ++pc) {
@@ -178,6 +179,27 @@ DQ_HD inline void eval_program(const PredInsn* code, int n, const uint8_t* pool,
         break;
       }
       case DQ_P_CAST: cast_value(st[sp - 1], ins.arg); break;
+      case kPredMatch: {  // Like / RLike(column, literal): NULL where the column is
+        const DevColumn& c = cols[ins.arg];
+        Val v = make(0, 0.0, VT_BOOL, col_valid(c, row) ? 0 : 1);
+#if defined(__HIP_DEVICE_COMPILE__)
+        // dq_match_mask_kernel has walked the row (a NULL row's bit is 0)
+        v.i = (int64_t)((ms.words[ins.i64 * ms.words_per_mask + (row >> 6)] >> (row & 63)) & 1ull);
+#else
+        if (!v.null) {  // the same walk over the same image, here
+          const uint8_t* img = ms.images + ms.offsets[ins.i64];
+          uint32_t head[4];
+          __builtin_memcpy(head, img, sizeof(head));
+          const uint8_t* cmap = img + regex::kRegexHeaderBytes;
+          const uint16_t* table = reinterpret_cast<const uint16_t*>(cmap + 256);
+          const int32_t b = c.offsets[row], e = c.offsets[row + 1];
+          v.i = regex::regex_walk(cmap, table, head[1], head[2], Bytes{static_cast<const uint8_t*>(c.values) + b},
+                                  (int64_t)(e - b)) ? 1 : 0;
+        }
+#endif
+        st[sp++] = v;
+        break;
+      }
       case DQ_P_TRUE: st[sp++] = make(1, 0.0, VT_BOOL, 0); break;
       case DQ_P_FALSE: st[sp++] = make(0, 0.0, VT_BOOL, 0); break;
       case DQ_P_COALESCE: {

@@ -8,8 +8,11 @@
 //   - `$` (Pattern.Dollar without MULTILINE) holds at the end of input, before a final \n not
 //     preceded by \r, before a final \r, U+0085, U+2028 or U+2029, and before a final \r\n;
 //   - lazy quantifiers accept the language of the greedy ones.
-// A pattern that can match the empty string is declined: its leftmost match may be empty where a
-// later one is not, which a DFA cannot tell (regexp_extract(...) != "" needs a NON-empty group 0).
+// In the find-non-empty mode (PatternMatch) a pattern that can match the empty string is declined:
+// its leftmost match may be empty where a later one is not, which a DFA cannot tell
+// (regexp_extract(...) != "" needs a NON-empty group 0).  The find mode (RLIKE: Matcher.find(0), any
+// match) answers such patterns; compile_like builds the whole-value DFA of a SQL LIKE pattern from
+// its own text.  All three share the subset construction and the image format.
 #include "dq_regex.h"
 
 #include <algorithm>
@@ -403,12 +406,14 @@ enum NodeKind : uint8_t { N_EPS, N_BYTE, N_MATCH, N_END, N_COND };
 struct Node {
   uint8_t kind = N_EPS, lo = 0, hi = 0;
   int out = -1;           // N_BYTE: target; N_COND: target taken unless the previous byte was \r
+  int tag = 0;            // compile_like: 2 * (number of % before the node) + (1: inside that %'s loop)
   std::vector<int> eps;   // N_EPS
 };
 
 struct Nfa {
   std::vector<Node> nodes;
   bool failed = false;
+  int cur_tag = 0;  // stamped on every node added
 
   int add(uint8_t kind) {
     if ((int)nodes.size() >= kMaxNfaNodes) {
@@ -417,7 +422,22 @@ struct Nfa {
     }
     nodes.push_back(Node());
     nodes.back().kind = kind;
+    nodes.back().tag = cur_tag;
     return (int)nodes.size() - 1;
+  }
+  // from --[one code point]--> to, for LIKE's `_` and `%`: a lead byte and the continuation bytes
+  // its length asks for.  On valid UTF-8 that is exactly "any code point"; the three continuation
+  // nodes are shared by the lead classes, so a subset carries at most three states per position.
+  void any_cp(int from, int to) {
+    byte_edge(from, 0x00, 0x7F, to);
+    const int c1 = add(N_EPS), c2 = add(N_EPS), c3 = add(N_EPS);
+    if (failed) return;
+    byte_edge(from, 0xC0, 0xDF, c1);
+    byte_edge(from, 0xE0, 0xEF, c2);
+    byte_edge(from, 0xF0, 0xF7, c3);
+    byte_edge(c3, 0x80, 0xBF, c2);
+    byte_edge(c2, 0x80, 0xBF, c1);
+    byte_edge(c1, 0x80, 0xBF, to);
   }
   void eps(int from, int to) {
     if (!failed) nodes[from].eps.push_back(to);
@@ -620,43 +640,32 @@ std::vector<uint8_t> Dfa::image() const {
   return out;
 }
 
-bool compile(const uint8_t* pattern, int32_t len, Dfa* out, std::string* err) {
+namespace {
+
+// The image of "every row matches": the walk starts in the accept row and never leaves it.
+void always_dfa(Dfa* out) {
+  out->n_states = 1;
+  out->n_cols = 2;  // one byte column and the end-of-input column, both back to row 0
+  out->start_row = kRegexAccept;
+  std::memset(out->cmap, 0, sizeof(out->cmap));
+  out->table.assign(2, 0);
+}
+
+// Subset construction over `nfa` from the closures of start_free and start_caret.
+//   search: the unanchored start's closure is re-added to every subset (find); without it the walk
+//           is anchored at the first byte (LIKE).
+//   accept_start: a start closure that already holds N_MATCH gives the always-matching image
+//           (find, LIKE); without it the caller has ruled that out (find-non-empty).
+//   prune: compile_like's subsets drop every node that lies before the last % whose loop they hold
+//           (whatever such a node can still reach, that loop reaches too), which keeps the DFA of
+//           '%a__%b__' the sum, not the product, of its parts'.
+// `who` / `dfa` word the declines ("regex" / "search DFA", "LIKE" / "DFA").
+bool construct(const Nfa& nfa, int start_free, int start_caret, bool any_dollar, bool search, bool accept_start,
+               bool prune, const char* who, const char* dfa, Dfa* out, std::string* err) {
   auto decline = [&](const std::string& m) {
     if (err) *err = m;
     return false;
   };
-  if (len < 0 || (len > 0 && !pattern)) return decline("regex: NULL pattern");
-  if (len > kMaxPatternBytes) return decline("regex: a pattern longer than " + std::to_string(kMaxPatternBytes) + " bytes is not supported on the GPU path");
-  Parser ps;
-  ps.p = pattern;
-  ps.n = len;
-  std::vector<Branch> branches;
-  if (!ps.parse_top(&branches)) return decline(ps.err);
-  for (const Branch& b : branches)
-    if (ps.nullable(b.ast))
-      return decline("regex: a pattern that can match the empty string at offset 0 is not supported on the GPU path "
-                     "(its leftmost match may be empty where a later one is not)");
-
-  Nfa nfa;
-  const int match = nfa.add(N_MATCH), end = nfa.add(N_END);
-  const int start_free = nfa.add(N_EPS), start_caret = nfa.add(N_EPS);
-  bool any_dollar = false;
-  for (const Branch& b : branches) {
-    int s, e;
-    nfa.build(ps.ast, b.ast, &s, &e);
-    if (nfa.failed) break;
-    nfa.eps(b.caret ? start_caret : start_free, s);
-    if (b.dollar) {
-      nfa.dollar(e, end);
-      any_dollar = true;
-    } else {
-      nfa.eps(e, match);
-    }
-  }
-  if (nfa.failed)
-    return decline("regex: the pattern needs more than " + std::to_string(kMaxNfaNodes) +
-                   " NFA nodes (counted repetitions are unrolled) at offset 0: not supported on the GPU path");
-
   // byte intervals on which every edge agrees
   bool cut[257] = {};
   cut[0] = cut[256] = true;
@@ -674,6 +683,15 @@ bool compile(const uint8_t* pattern, int32_t len, Dfa* out, std::string* err) {
   }
   const int n_iv = (int)rep.size();
 
+  auto pruned = [&](std::vector<int>& set) {
+    if (!prune) return;
+    int last = -1;
+    for (int v : set)
+      if (nfa.nodes[v].tag & 1) last = std::max(last, nfa.nodes[v].tag);
+    if (last < 0) return;
+    set.erase(std::remove_if(set.begin(), set.end(), [&](int v) { return nfa.nodes[v].tag < last - 1; }), set.end());
+  };
+
   // subset construction; state 0 = accept (absorbing), state 1 = start
   Subset sub(nfa);
   // (each subset is stored once, as its map key; `sets` points at the keys, which never move)
@@ -686,15 +704,21 @@ bool compile(const uint8_t* pattern, int32_t len, Dfa* out, std::string* err) {
   rows.push_back(std::vector<uint16_t>((size_t)n_iv + 1, 0));
   // the unanchored start's closure after a byte that is / is not \r: added to every subset
   std::vector<int> restart[2];
-  for (int cr = 0; cr < 2; ++cr) {
-    sub.begin();
-    sub.close(start_free, cr != 0, restart[cr]);
-  }
+  if (search)
+    for (int cr = 0; cr < 2; ++cr) {
+      sub.begin();
+      sub.close(start_free, cr != 0, restart[cr]);
+    }
   {
     std::vector<int> s0;
     sub.begin();
-    sub.close(start_free, false, s0);
-    sub.close(start_caret, false, s0);
+    bool hit = sub.close(start_free, false, s0);
+    hit = sub.close(start_caret, false, s0) || hit;
+    if (hit && accept_start) {
+      always_dfa(out);
+      return true;
+    }
+    pruned(s0);
     std::sort(s0.begin(), s0.end());
     subset_nodes += s0.size();
     sets.push_back(&ids.emplace(s0, 1).first->first);
@@ -731,15 +755,16 @@ bool compile(const uint8_t* pattern, int32_t len, Dfa* out, std::string* err) {
         seen[taken] = 0;
         continue;
       }
+      pruned(to);
       std::sort(to.begin(), to.end());
       auto it = ids.find(to);
       if (it == ids.end()) {
         if ((int)sets.size() >= kMaxStates)
-          return decline("regex: the pattern's search DFA has more than " + std::to_string(kMaxStates) +
+          return decline(std::string(who) + ": the pattern's " + dfa + " has more than " + std::to_string(kMaxStates) +
                          " states (cap reached at offset 0): not supported on the GPU path");
         subset_nodes += to.size();
         if (subset_nodes > (size_t)kMaxSubsetNodes)
-          return decline("regex: the pattern's search DFA holds more than " + std::to_string(kMaxSubsetNodes) +
+          return decline(std::string(who) + ": the pattern's " + dfa + " holds more than " + std::to_string(kMaxSubsetNodes) +
                          " NFA nodes in its subsets (cap reached at offset 0): not supported on the GPU path");
         it = ids.emplace(to, (int)sets.size()).first;
         sets.push_back(&it->first);
@@ -772,7 +797,7 @@ bool compile(const uint8_t* pattern, int32_t len, Dfa* out, std::string* err) {
   const int n_cols = (int)col_src.size() + 1;
   const size_t entries = (size_t)n_states * n_cols;
   if (entries * sizeof(uint16_t) > (size_t)kMaxTableBytes || entries > 65535)
-    return decline("regex: the pattern's transition table (" + std::to_string(n_states) + " states x " +
+    return decline(std::string(who) + ": the pattern's transition table (" + std::to_string(n_states) + " states x " +
                    std::to_string(n_cols) + " columns at offset 0) is over the " + std::to_string(kMaxTableBytes) +
                    "-byte LDS budget: not supported on the GPU path");
   out->n_states = (uint32_t)n_states;
@@ -786,6 +811,106 @@ bool compile(const uint8_t* pattern, int32_t len, Dfa* out, std::string* err) {
   }
   return true;
 }
+
+}  // namespace
+
+bool compile_mode(const uint8_t* pattern, int32_t len, Mode mode, Dfa* out, std::string* err) {
+  auto decline = [&](const std::string& m) {
+    if (err) *err = m;
+    return false;
+  };
+  if (mode != kFindNonEmpty && mode != kFind) return decline("regex: unknown matching mode");
+  if (len < 0 || (len > 0 && !pattern)) return decline("regex: NULL pattern");
+  if (len > kMaxPatternBytes) return decline("regex: a pattern longer than " + std::to_string(kMaxPatternBytes) + " bytes is not supported on the GPU path");
+  Parser ps;
+  ps.p = pattern;
+  ps.n = len;
+  std::vector<Branch> branches;
+  if (!ps.parse_top(&branches)) return decline(ps.err);
+  if (mode == kFindNonEmpty)
+    for (const Branch& b : branches)
+      if (ps.nullable(b.ast))
+        return decline("regex: a pattern that can match the empty string at offset 0 is not supported on the GPU path "
+                       "(its leftmost match may be empty where a later one is not)");
+
+  Nfa nfa;
+  const int match = nfa.add(N_MATCH), end = nfa.add(N_END);
+  const int start_free = nfa.add(N_EPS), start_caret = nfa.add(N_EPS);
+  bool any_dollar = false;
+  for (const Branch& b : branches) {
+    int s, e;
+    nfa.build(ps.ast, b.ast, &s, &e);
+    if (nfa.failed) break;
+    nfa.eps(b.caret ? start_caret : start_free, s);
+    if (b.dollar) {
+      nfa.dollar(e, end);
+      any_dollar = true;
+    } else {
+      nfa.eps(e, match);
+    }
+  }
+  if (nfa.failed)
+    return decline("regex: the pattern needs more than " + std::to_string(kMaxNfaNodes) +
+                   " NFA nodes (counted repetitions are unrolled) at offset 0: not supported on the GPU path");
+  return construct(nfa, start_free, start_caret, any_dollar, true, mode == kFind, false, "regex", "search DFA", out, err);
+}
+
+bool compile(const uint8_t* pattern, int32_t len, Dfa* out, std::string* err) {
+  return compile_mode(pattern, len, kFindNonEmpty, out, err);
+}
+
+bool compile_like(const uint8_t* pattern, int32_t len, Dfa* out, std::string* err) {
+  auto decline = [&](const std::string& m) {
+    if (err) *err = m;
+    return false;
+  };
+  if (len < 0 || (len > 0 && !pattern)) return decline("LIKE: NULL pattern");
+  if (len > kMaxPatternBytes) return decline("LIKE: a pattern longer than " + std::to_string(kMaxPatternBytes) + " bytes is not supported on the GPU path");
+  Parser ps;  // (its UTF-8 decoder only)
+  ps.p = pattern;
+  ps.n = len;
+  Nfa nfa;
+  nfa.cur_tag = 1 << 30;  // the end node outlives every pruning
+  const int match = nfa.add(N_MATCH), end = nfa.add(N_END);
+  nfa.cur_tag = 0;
+  const int start = nfa.add(N_EPS), unused = nfa.add(N_EPS);
+  int cur = start, stars = 0;
+  bool open_tail = false;  // the pattern read so far ends in %
+  while (!ps.eof() && !nfa.failed) {
+    const int32_t where = ps.at;
+    uint32_t cp;
+    if (!ps.next_cp(&cp)) return decline("LIKE: invalid UTF-8 in the pattern at offset " + std::to_string(where));
+    if (cp == '\\')
+      return decline("LIKE: a backslash in the pattern at offset " + std::to_string(where) +
+                     " is not supported on the GPU path (Spark's LIKE escapes are not evaluated here)");
+    if (cp == '%') {
+      if (open_tail) continue;  // %% is %
+      ++stars;
+      nfa.cur_tag = 2 * stars + 1;
+      const int loop = nfa.add(N_EPS);
+      nfa.eps(cur, loop);
+      nfa.any_cp(loop, loop);
+      nfa.cur_tag = 2 * stars;
+      cur = loop;
+      open_tail = true;
+      continue;
+    }
+    // (a trailing % never gets here again: what follows is matched from the loop node)
+    open_tail = false;
+    const int nxt = nfa.add(N_EPS);
+    if (cp == '_') nfa.any_cp(cur, nxt);
+    else nfa.cp_range(cur, cp, cp, nxt);
+    cur = nxt;
+  }
+  if (nfa.failed)
+    return decline("LIKE: the pattern needs more than " + std::to_string(kMaxNfaNodes) +
+                   " NFA nodes at offset 0: not supported on the GPU path");
+  // A trailing %: every continuation accepts, so the state is the accept row itself and the walker
+  // stops reading there.  Otherwise only the end of the input accepts.
+  nfa.eps(cur, open_tail ? match : end);
+  return construct(nfa, start, unused, false, false, true, true, "LIKE", "DFA", out, err);
+}
+
 
 }  // namespace regex
 }  // namespace dq

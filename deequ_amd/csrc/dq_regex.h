@@ -74,9 +74,25 @@ struct Dfa {
   std::vector<uint8_t> image() const;
 };
 
+// What a compiled image answers about one row's bytes.  The image format and the walker are the
+// same for all three; only the construction differs.
+enum Mode : int32_t {
+  kFindNonEmpty = 0,  // Matcher.find() with a non-empty group 0 (PatternMatch, RowLevelSchemaValidator)
+  kFind = 1,          // Matcher.find(0): any match, an empty one included (RLIKE)
+  kFull = 2           // the whole value matches a LIKE pattern (compile_like only)
+};
+
 // Compiles pattern[0 .. len) (UTF-8 text of a Java regex).  False = not in the supported subset
 // (or over a construction bound): *err names the construct and its byte offset.
 bool compile(const uint8_t* pattern, int32_t len, Dfa* out, std::string* err);
+// ... in kFindNonEmpty (what compile() is) or kFind: the unanchored search without the "can match
+// the empty string" decline; a pattern whose unanchored (or ^-anchored) part is nullable matches
+// every row, and its image starts in the accept row.
+bool compile_mode(const uint8_t* pattern, int32_t len, Mode mode, Dfa* out, std::string* err);
+// Compiles the SQL LIKE pattern[0 .. len) (UTF-8; `_` one code point, `%` any sequence of code
+// points, line terminators included; everything else itself) anchored at both ends.  A backslash
+// is declined (LIKE escapes are not evaluated here), as is a pattern over a construction bound.
+bool compile_like(const uint8_t* pattern, int32_t len, Dfa* out, std::string* err);
 
 }  // namespace regex
 }  // namespace dq

@@ -33,7 +33,89 @@ __device__ __forceinline__ uint32_t step4(const uint8_t* cmap, const uint16_t* t
   return table[s + c3];
 }
 
+// The workgroup's copy of an image's byte map and table (the image is padded to 16 bytes, so whole
+// words cover it); the caller synchronises.
+__device__ inline void stage_image(const uint32_t* img, uint32_t n_entries, uint8_t* lds) {
+  const uint32_t words = (256u + 2u * n_entries + 3u) >> 2;
+  const uint32_t* src = img + regex::kRegexHeaderBytes / 4;
+  uint32_t* dst = reinterpret_cast<uint32_t*>(lds);
+  for (uint32_t i = threadIdx.x; i < words; i += kBlock) dst[i] = src[i];
+}
+
+// One row's bytes [b, e) of the heap behind `rs`, from the start row: 16 bytes per load, then 4,
+// then 1 -- never a byte outside the row -- and no further load once the state is the accept row.
+__device__ __forceinline__ bool walk_row(const __amdgpu_buffer_rsrc_t rs, const uint8_t* cmap, const uint16_t* table,
+                                         uint32_t n_cols, uint32_t start_row, int32_t b, int32_t e) {
+  uint32_t s = start_row;
+  int32_t p = b;
+  while (s != regex::kRegexAccept && e - p >= 16) {
+    const auto v = __builtin_amdgcn_raw_buffer_load_b128(rs, p, 0, 0);
+    s = step4(cmap, table, s, v[0]);
+    s = step4(cmap, table, s, v[1]);
+    s = step4(cmap, table, s, v[2]);
+    s = step4(cmap, table, s, v[3]);
+    p += 16;
+  }
+  while (s != regex::kRegexAccept && e - p >= 4) {
+    s = step4(cmap, table, s, __builtin_amdgcn_raw_buffer_load_b32(rs, p, 0, 0));
+    p += 4;
+  }
+  while (s != regex::kRegexAccept && p < e) {
+    s = regex::regex_step(cmap, table, s, __builtin_amdgcn_raw_buffer_load_b8(rs, p, 0, 0));
+    ++p;
+  }
+  return regex::regex_finish(table, n_cols, s);
+}
+
 }  // namespace
+
+// LIKE / RLIKE of a predicate: blockIdx.y is a match task {column, DFA}; the workgroup stages the
+// image as dq_regex_kernel does, then each wave takes 64 consecutive rows (word w of the mask), one
+// lane walks one row, and lane 0 stores the wave's ballot: bit r = row r matched; a NULL row and a
+// lane past n_rows give 0.  No atomics: every word is written once, by one wave.
+__global__ __launch_bounds__(kBlock) void dq_match_mask_kernel(const MatchTask* __restrict__ tasks,
+                                                               const DevColumn* __restrict__ cols,
+                                                               const uint8_t* __restrict__ dfas, int64_t n_rows,
+                                                               uint64_t* __restrict__ out, int64_t words_per_mask) {
+  extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
+  const MatchTask task = tasks[blockIdx.y];
+  const uint32_t* img = reinterpret_cast<const uint32_t*>(dfas + task.dfa_off);
+  const uint32_t n_cols = img[1], start_row = img[2], n_entries = img[3];
+  stage_image(img, n_entries, lds);
+  __syncthreads();
+  const uint8_t* cmap = lds;
+  const uint16_t* table = reinterpret_cast<const uint16_t*>(lds + 256);
+
+  const DevColumn& col = cols[task.column];
+  const uint32_t heap_end = (uint32_t)col.offsets[n_rows];
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+      const_cast<uint8_t*>(static_cast<const uint8_t*>(col.values)), 0, (int)heap_end, 0x00020000);
+  const int lane = threadIdx.x & 63;
+  const int64_t n_words = (n_rows + 63) >> 6;
+  uint64_t* out_m = out + (int64_t)blockIdx.y * words_per_mask;
+  for (int64_t w = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); w < n_words;
+       w += (int64_t)gridDim.x * (kBlock / 64)) {
+    const int64_t row = (w << 6) + lane;
+    bool hit = false;
+    if (row < n_rows && (!col.validity || bit_at(col.validity, row)))
+      hit = walk_row(rs, cmap, table, n_cols, start_row, col.offsets[row], col.offsets[row + 1]);
+    const uint64_t word = __ballot(hit);
+    if (lane == 0) out_m[w] = word;
+  }
+}
+
+hipError_t launch_match_mask(const MatchTask* d_tasks, int n_tasks, const DevColumn* d_cols, const uint8_t* d_dfas,
+                             uint32_t lds_bytes, int64_t n_rows, uint64_t* d_out, int64_t words_per_mask,
+                             hipStream_t stream) {
+  if (n_tasks <= 0 || n_rows <= 0) return hipSuccess;
+  const int64_t n_words = (n_rows + 63) >> 6;
+  int64_t blocks = (n_words + 3) / 4;
+  const int64_t cap = std::max<int64_t>(1, 4096 / n_tasks);
+  if (blocks > cap) blocks = cap;
+  hipLaunchKernelGGL(dq_match_mask_kernel, dim3((unsigned)blocks, n_tasks), dim3(kBlock), lds_bytes, stream, d_tasks,
+                     d_cols, d_dfas, n_rows, d_out, words_per_mask);
+  return hipGetLastError();
+}
 
 __global__ __launch_bounds__(kBlock) void dq_regex_kernel(const RegexTask* __restrict__ tasks,
                                                           const DevColumn* __restrict__ cols,

@@ -22,6 +22,16 @@ Spark 2.2.2's literal typing and coercion:
   (the library evaluates Spark 2.2's Cast semantics: narrowing wraps, fractional -> integral is
   Java's saturating d2i / d2l); CAST(string AS DOUBLE) is DQ_P_CAST_DOUBLE.
 
+* `s [NOT] LIKE 'p'` and `s [NOT] RLIKE 'r'` (`REGEXP` is RLIKE) of a string column and one string
+  literal become DQ_P_COLUMN, DQ_P_LIT_STRING, DQ_P_LIKE | DQ_P_RLIKE: the library compiles the
+  pattern into a byte DFA (LIKE: `_` one code point, `%` any sequence, the whole value; RLIKE:
+  Matcher.find(0), an empty match included) and evaluates it as a match mask on the GPU.  Declined
+  by name: another left side (Spark casts it to string), a right side that is not one string
+  literal, any backslash sequence but `\\\\` in the pattern literal's source text (the only one
+  this tokenizer and Spark's unescapeSQLString certainly agree on; write `'^\\\\d{5}$'` as in
+  Spark), a LIKE pattern that still holds a backslash (LIKE escapes), and a pattern the compiler
+  declines (outside PatternMatch's regex subset, or a DFA over its bounds).
+
 Column names resolve case-insensitively, as Spark 2.2 does by default
 (`spark.sql.caseSensitive=false`); two columns equal but for case make a reference ambiguous.
 
@@ -69,7 +79,10 @@ def _integer_literal(v: int):
 
 
 # ----------------------------------------------------------------------------- lexer
-def _tokenize(text: str):
+def _tokenize(text: str, raws=None):
+    """The tokens of `text`.  raws (a dict, optional) receives {token index: the source text
+    between the quotes} of each string literal: LIKE / RLIKE check a pattern literal's backslashes
+    on it."""
     toks, i, n = [], 0, len(text)
     while i < n:
         ch = text[i]
@@ -86,6 +99,8 @@ def _tokenize(text: str):
                 j += 1
             if j >= n:
                 raise PredicateSyntaxError("unterminated string literal in %r" % text)
+            if raws is not None:
+                raws[len(toks)] = text[i + 1:j]
             toks.append(("STR", "".join(buf)))
             i = j + 1
             continue
@@ -139,7 +154,8 @@ def _tokenize(text: str):
 class _Parser:
     def __init__(self, text: str):
         self.text = text
-        self.toks = _tokenize(text)
+        self.raws = {}  # token index -> source text of a string literal
+        self.toks = _tokenize(text, self.raws)
         self.pos = 0
 
     def peek(self):
@@ -209,6 +225,10 @@ class _Parser:
             hi = self.value()
             node = ("and", ("cmp", ">=", left, lo), ("cmp", "<=", left, hi))
             return ("not", node) if negated else node
+        for word in ("LIKE", "RLIKE", "REGEXP"):
+            if self.keyword(word):
+                node = self.pattern_predicate("like" if word == "LIKE" else "rlike", word, left)
+                return ("not", node) if negated else node
         if negated:
             raise PredicateSyntaxError("dangling NOT in %r" % self.text)
         if self.keyword("IS"):
@@ -217,6 +237,20 @@ class _Parser:
                 raise PredicateSyntaxError("expected NULL after IS in %r" % self.text)
             return ("isnotnull" if neg else "isnull", left)
         return ("truth", left)
+
+    def pattern_predicate(self, kind: str, word: str, left):
+        """`left LIKE | RLIKE | REGEXP <right>`: ("like" | "rlike", left, right).  A right side of
+        string literals carries their source text, ("lit", "pattern", value, raw), so that the
+        compiler can decline every backslash sequence but `\\\\`."""
+        start = self.pos
+        t = self.peek()
+        if t[0] == "EOF" or (t[0] == "ID" and t[1].upper() in ("LIKE", "RLIKE", "REGEXP", "AND", "OR", "NOT")):
+            raise PredicateSyntaxError("expected a pattern after %s in %r" % (word, self.text))
+        right = self.value()
+        if right[0] == "lit" and right[1] == "str":
+            raw = "".join(self.raws[k] for k in range(start, self.pos))
+            right = ("lit", "pattern", right[2], raw)
+        return (kind, left, right)
 
     def value(self):
         node = self._operand()
@@ -556,6 +590,47 @@ class _Compiler:
         self.emit_value(b, "int")
         self.emit(self._OPS[op], L.DQ_CMP_AS_INT64)
 
+    def emit_pattern(self, kind, left, right):
+        """Like / RLike(string column, string literal): DQ_P_COLUMN, DQ_P_LIT_STRING, DQ_P_LIKE |
+        DQ_P_RLIKE.  Everything Spark would answer in a way this path cannot vouch for is declined."""
+        name = "LIKE" if kind == "like" else "RLIKE"
+        if left[0] != "col":
+            what = {"lit": "a literal", "coalesce": "COALESCE(...)", "cast": "CAST(...)"}.get(left[0], "an expression")
+            raise UnsupportedPredicate("%s of %s: the left side must be a string column on the GPU path" % (name, what))
+        idx, dtype = self.column(left[1])
+        if dtype != "string":
+            raise UnsupportedPredicate("%s of the %s column %s: Spark casts it to string, the GPU path takes "
+                                       "a string column only" % (name, dtype, left[1]))
+        if right[0] != "lit" or right[1] != "pattern":
+            what = ("a column" if right[0] == "col" else "NULL" if right[0] == "lit" and right[1] == "null"
+                    else "not a string literal")
+            raise UnsupportedPredicate("%s pattern is %s: the right side must be one string literal on the GPU path"
+                                       % (name, what))
+        pattern, raw = right[2], right[3]
+        k = 0
+        while k < len(raw):  # the source text: only `\\` is an escape both unescape rules agree on
+            if raw[k] == "\\":
+                if k + 1 >= len(raw) or raw[k + 1] != "\\":
+                    seq = raw[k:k + 2] if k + 1 < len(raw) else "a trailing \\"
+                    raise UnsupportedPredicate(
+                        "%s pattern literal holds the backslash sequence %s: only \\\\ (one backslash) is accepted "
+                        "in the source text of a pattern on the GPU path" % (name, seq))
+                k += 2
+            else:
+                k += 1
+        if kind == "like" and "\\" in pattern:
+            raise UnsupportedPredicate("LIKE pattern holds a backslash: Spark's LIKE escapes are not evaluated "
+                                       "on the GPU path")
+        b = pattern.encode("utf-8")
+        try:  # the library's own compiler decides what it can answer exactly
+            L.diag_regex_match(b, b"", "full" if kind == "like" else "find")
+        except L.UnsupportedOnGpu as e:
+            raise UnsupportedPredicate("%s pattern %r: %s" % (name, pattern, str(e).split(": ", 1)[-1]))
+        self.emit(L.DQ_P_COLUMN, idx)
+        self.emit(L.DQ_P_LIT_STRING, len(b), i64=len(self.pool))
+        self.pool += b
+        self.emit(L.DQ_P_LIKE if kind == "like" else L.DQ_P_RLIKE)
+
     def emit_bool(self, node):
         t = node[0]
         if t == "cmp":
@@ -603,6 +678,8 @@ class _Compiler:
                     self.emit_cmp("=", x, item)
                 if k:
                     self.emit(L.DQ_P_OR)
+        elif t in ("like", "rlike"):
+            self.emit_pattern(t, node[1], node[2])
         elif t == "truth":
             v = node[1]
             if v[0] == "lit" and v[1] == "bool":
@@ -611,7 +688,7 @@ class _Compiler:
                 self.emit(L.DQ_P_COLUMN, self.column(v[1])[0])
             elif (v[0] == "cast" and v[2] == "bool") or (v[0] == "coalesce" and self.stype(v) == "bool"):
                 self.emit_value(v, "int")
-            elif v[0] in ("or", "and", "not", "cmp", "in", "isnull", "isnotnull", "truth"):
+            elif v[0] in ("or", "and", "not", "cmp", "in", "isnull", "isnotnull", "truth", "like", "rlike"):
                 self.emit_bool(v)
             else:
                 raise UnsupportedPredicate("non-boolean predicate")

@@ -159,7 +159,19 @@ typedef enum dq_pred_opcode {
   DQ_P_IS_NULL = 20,   /* pop value; push boolean (never NULL)                              */
   DQ_P_IS_NOT_NULL = 21,
   DQ_P_AND = 30, DQ_P_OR = 31, DQ_P_NOT = 32,
-  DQ_P_TRUE = 33, DQ_P_FALSE = 34
+  DQ_P_TRUE = 33, DQ_P_FALSE = 34,
+  DQ_P_LIKE = 40,      /* pop pattern, value; push boolean: Catalyst's Like(left, right) of the
+                           analyzed expression (before LikeSimplification).  `_` is one code point,
+                           `%` any sequence of them (line terminators included), every other
+                           character itself; the whole value must match; NULL where the value is.
+                           Accepted only as the triple DQ_P_COLUMN (a utf8 column), DQ_P_LIT_STRING,
+                           DQ_P_LIKE; any other operand shape, a pattern that holds a backslash and
+                           a pattern whose DFA is over the construction bounds are
+                           DQ_ERR_UNSUPPORTED.                                               */
+  DQ_P_RLIKE = 41      /* the same for RLike(left, right) (RLIKE / REGEXP): TRUE when
+                           Pattern.compile(regex).matcher(value).find(0) -- any match, an empty one
+                           included.  The regex subset and its declines are PatternMatch's
+                           (DESIGN.md), without the "can match the empty string" decline.       */
 } dq_pred_opcode;
 
 #define DQ_CMP_AS_INT64 0

@@ -82,6 +82,18 @@ dq_status dq_diag_uuid_pack(const uint8_t* key, int32_t len, uint64_t* words, ui
 dq_status dq_diag_regex_match(const uint8_t* pattern, int32_t pattern_len, const uint8_t* text, int64_t n,
                               int32_t* matched, int32_t* n_states, int32_t* n_classes);
 
+/* dq_diag_regex_match in one of the compiler's three matching modes: 0 find with a non-empty group
+ * 0 (what dq_diag_regex_match is), 1 find (RLIKE: an empty match counts), 2 full (pattern is a SQL
+ * LIKE pattern and the whole text must match).  image (may be NULL) receives the compiled DFA image
+ * when image_capacity holds it; *image_len (may be NULL) = its size either way. */
+dq_status dq_diag_regex_match_mode(const uint8_t* pattern, int32_t pattern_len, int32_t mode, const uint8_t* text,
+                                   int64_t n, int32_t* matched, int32_t* n_states, int32_t* n_classes,
+                                   uint8_t* image, int64_t image_capacity, int64_t* image_len);
+
+/* LIKE / RLIKE match tasks of a plan (distinct (column, pattern, mode) over all its predicates and
+ * filters) and the distinct DFA images they use.  Host bookkeeping only. */
+dq_status dq_diag_plan_match_tasks(dq_plan* plan, int32_t* n_tasks, int32_t* n_images);
+
 /* Host build of KLLSketch's whole layout (deequ_amd/csrc/dq_kll.cpp: the reference's sequential
  * sketch; no GPU): values[r] is row r, NULL where valid[r] == 0 (valid may be NULL: no NULLs); the
  * rows are cut into slabs of slab_rows, each sketched as one reference partition, and the slabs merged
