@@ -15,6 +15,7 @@ from .analyzers import (Analyzer, ApproxCountDistinct, ApproxQuantile, ApproxQua
                         StandardDeviation, StandardScanShareableAnalyzer, Sum, Uniqueness,
                         UniqueValueRatio)
 from .frequencies import FrequenciesAndNumRows, FrequencyTable
+from .distance import Distance
 from .engine import Plan, current_device, run_scan, set_device
 from .metrics import (BucketDistribution, BucketValue, KLLMetric, Distribution, DistributionValue, DoubleMetric, EmptyStateException, Entity,
                       Failure, HistogramMetric, KeyedDoubleMetric,

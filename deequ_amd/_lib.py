@@ -130,6 +130,11 @@ class DqFreqSummary(Structure):
                 ("grouped_rows", c_int64), ("entropy", c_double)]
 
 
+class DqFreqDistance(Structure):
+    _fields_ = [("linf_simple", c_double), ("n", c_int64), ("m", c_int64), ("groups_a", c_int64),
+                ("groups_b", c_int64), ("groups_common", c_int64)]
+
+
 class DqFreqWire(Structure):
     _fields_ = [("ctrl", c_uint64), ("count", c_int64), ("k0", c_uint64), ("k1", c_uint64)]
 
@@ -246,6 +251,7 @@ SIGNATURES = {
     "dq_freq_top": (c_int, [c_void_p, c_int, POINTER(DqFreqGroup), c_int64, c_void_p, c_int64,
                             POINTER(c_int64), POINTER(c_int64)]),
     "dq_freq_merge": (c_int, [c_void_p, c_void_p]),
+    "dq_freq_linf_distance": (c_int, [c_void_p, c_void_p, POINTER(DqFreqDistance)]),
     "dq_freq_import": (c_int, [c_void_p, POINTER(DqFreqGroup), c_int64, c_void_p, c_int64]),
     "dq_freq_export_flat": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int,
                                     POINTER(c_int64), POINTER(c_int64)]),

@@ -884,6 +884,132 @@ __global__ void dq_freq_lookup_kernel(FreqTable T, const uint8_t* key, uint32_t 
   }
 }
 
+// ---- Distance (Distance.scala:43-87, categoricalDistance): the L-infinity distance of two
+// tables' relative frequencies, max over the union of keys of |ca / n - cb / m|.  Both tables
+// stay as they are: the passes only read slot images (launch boundary: every insert is visible).
+//  1. totals: n = the sum of a table's counts (num_rows also counts rows without a key), as the
+//     sums of the counts' 32-bit halves, which cannot wrap over 2^32 slots; the host adds them.
+//  2. one directed pass X -> Y: every occupied slot of X rebuilds its key's hash (as slot_hash),
+//     probes Y as dq_freq_lookup_kernel does and forms |cx / nx - cy / ny| in fp64 (a miss: cy = 0).
+//     The values are non-negative and finite, so their bit patterns order as unsigned integers:
+//     wave maximum, the workgroup's LDS, one 64-bit atomic max per workgroup -- any order gives
+//     the same bits.  Hits are counted from wave ballots.  The pass Y -> X covers the keys only
+//     in Y (a key in both gives the same value both ways).
+// The loops run whole workgroups past the last slot together (a capacity is a multiple of kBlock),
+// so every ballot and shuffle sees all 64 lanes.
+__device__ inline unsigned long long wave_max_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long w = __shfl_xor(v, o);
+    v = w > v ? w : v;
+  }
+  return v;
+}
+
+__device__ inline unsigned long long wave_sum_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+
+__global__ __launch_bounds__(kBlock) void dq_freq_totals_kernel(const FreqSlot* __restrict__ slots, uint64_t n_slots,
+                                                                unsigned long long* tot) {
+  __shared__ unsigned long long part[kBlock / 64][3];
+  unsigned long long lo = 0, hi = 0, groups = 0;
+  for (uint64_t base = (uint64_t)blockIdx.x * kBlock; base < n_slots; base += (uint64_t)gridDim.x * kBlock) {
+    const uint64_t s = base + threadIdx.x;
+    if (s >= n_slots) continue;
+    const unsigned long long ctrl = slots[s].ctrl, count = slots[s].count;
+    if (!(ctrl & kReady)) continue;
+    lo += count & 0xFFFFFFFFull;
+    hi += count >> 32;
+    groups += 1;
+  }
+  lo = wave_sum_u64(lo);
+  hi = wave_sum_u64(hi);
+  groups = wave_sum_u64(groups);
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    part[wave][0] = lo;
+    part[wave][1] = hi;
+    part[wave][2] = groups;
+  }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    unsigned long long v = 0;
+    for (int w = 0; w < kBlock / 64; ++w) v += part[w][threadIdx.x];
+    if (v) atomicAdd(&tot[threadIdx.x], v);
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void dq_freq_linf_kernel(FreqTable X, FreqTable Y, double nx, double ny,
+                                                              unsigned long long* out_max,
+                                                              unsigned long long* out_common) {
+  __shared__ unsigned long long part[kBlock / 64][2];
+  const uint64_t n_slots = X.mask + 1;
+  unsigned long long best = 0ull;  // bits of +0.0
+  unsigned long long hits = 0ull;  // wave-uniform
+  for (uint64_t base = (uint64_t)blockIdx.x * kBlock; base < n_slots; base += (uint64_t)gridDim.x * kBlock) {
+    const uint64_t s = base + threadIdx.x;
+    FreqSlot e{};
+    if (s < n_slots) e = X.slots[s];
+    const uint32_t len = (uint32_t)(e.ctrl & kLenMask);
+    const bool heap = (e.ctrl & kHeapKey) != 0;
+    bool occ = (e.ctrl & kReady) != 0;
+    // (a heap reference past the heap is never followed: such a group has no key to compare)
+    if (occ && heap && (e.k0 > X.heap_cap || (unsigned long long)len > X.heap_cap - e.k0)) occ = false;
+    bool hit = false;
+    if (occ) {
+      const uint8_t* px = X.heap + e.k0;  // (read only for a heap key)
+      const uint64_t h = heap ? hash_long(px, len) : hash_inline(e.k0, e.k1, len);
+      const uint32_t tag = tag_of(h);
+      const unsigned long long form = e.ctrl & (kLenMask | kHeapKey);
+      unsigned long long cy = 0ull;
+      for (uint64_t i = 0; i < kFreqSliceSlots; ++i) {
+        const FreqSlot y = Y.slots[probe_slot(Y, h, i)];
+        if (y.ctrl == 0ull) break;
+        if ((uint32_t)(y.ctrl >> 32) != tag || (y.ctrl & (kLenMask | kHeapKey)) != form) continue;
+        bool eq;
+        if (!heap) {
+          eq = y.k0 == e.k0 && y.k1 == e.k1;
+        } else {
+          eq = y.k0 <= Y.heap_cap && (unsigned long long)len <= Y.heap_cap - y.k0;
+          const uint8_t* py = Y.heap + y.k0;
+          for (uint32_t j = 0; eq && j < len; j += 8) {
+            const uint32_t n = len - j < 8 ? len - j : 8;
+            eq = ld_partial(px + j, n) == ld_partial(py + j, n);
+          }
+        }
+        if (eq) {
+          cy = y.count;
+          hit = true;
+          break;
+        }
+      }
+      const double d = fabs((double)e.count / nx - (double)cy / ny);
+      const unsigned long long bits = (unsigned long long)__double_as_longlong(d);
+      best = bits > best ? bits : best;
+    }
+    hits += (unsigned long long)__popcll(__ballot(hit));
+  }
+  best = wave_max_u64(best);
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    part[wave][0] = best;
+    part[wave][1] = hits;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long m = 0ull, c = 0ull;
+    for (int w = 0; w < kBlock / 64; ++w) {
+      m = part[w][0] > m ? part[w][0] : m;
+      c += part[w][1];
+    }
+    if (m) atomicMax(out_max, m);
+    if (out_common && c) atomicAdd(out_common, c);
+  }
+}
+
 // ---- multi-GPU key-hash partitioning (owner = a function of hash bits the table does not use
 // for its slot index, so every owner's keys still spread over its whole table): bits 11..30,
 // above the first probe (bits 0..10) and below any slice index (the top <= 22 bits); they
@@ -4743,6 +4869,23 @@ hipError_t launch_freq_lookup(const FreqTable& T, const uint8_t* d_key, uint32_t
                               hipStream_t stream, const FreqCompact* cmp) {
   hipLaunchKernelGGL(dq_freq_lookup_kernel, dim3(1), dim3(64), 0, stream, T, d_key, len, d_out,
                      cmp ? *cmp : FreqCompact{});
+  return hipGetLastError();
+}
+
+static unsigned freq_dist_blocks(const FreqTable& T) {
+  const uint64_t blocks = (T.mask + kBlock) / kBlock;
+  return (unsigned)(blocks < kFreqDistMaxBlocks ? blocks : kFreqDistMaxBlocks);
+}
+
+hipError_t launch_freq_totals(const FreqTable& T, unsigned long long* d_tot, hipStream_t stream) {
+  hipLaunchKernelGGL(dq_freq_totals_kernel, dim3(freq_dist_blocks(T)), dim3(kBlock), 0, stream, T.slots, T.mask + 1, d_tot);
+  return hipGetLastError();
+}
+
+hipError_t launch_freq_linf(const FreqTable& X, const FreqTable& Y, double nx, double ny, unsigned long long* d_max,
+                            unsigned long long* d_common, hipStream_t stream) {
+  hipLaunchKernelGGL(dq_freq_linf_kernel, dim3(freq_dist_blocks(X)), dim3(kBlock), 0, stream, X, Y, nx, ny, d_max,
+                     d_common);
   return hipGetLastError();
 }
 

@@ -112,6 +112,7 @@ struct dq_freq : Stager {
   std::vector<std::pair<unsigned long long, std::string>> top_cache;
   // dq_freq_export_flat's device result, kept from the sizing call to the filling call
   DevBuf d_flat_aux, d_flat, d_flat_bytes;
+  DevBuf d_dist;  // dq_freq_linf_distance's eight result words
   bool flat_valid = false;
   uint64_t flat_n = 0, flat_bytes = 0;
   void invalidate() {
@@ -1969,6 +1970,63 @@ extern "C" dq_status dq_freq_merge(dq_freq* dst, dq_freq* src) {
   if (hs[FC_GROUPS]) DQ_TRY(dst->import_runs(runs, (int64_t)hs[FC_GROUPS], hs[FC_HEAP_USED]));
   else dst->invalidate();
   dst->num_rows += src->num_rows;
+  return DQ_OK;
+}
+
+// Distance.categoricalDistance over two device states (Distance.scala:43-87): see dq_freq.hip
+// "Distance".  Words of a->d_dist: {max bits, common, a's lo / hi / groups, b's lo / hi / groups}.
+extern "C" dq_status dq_freq_linf_distance(dq_freq* a, dq_freq* b, dq_freq_distance* out) {
+  if (!a || !b) return fail(DQ_ERR_INVALID, "NULL table");
+  if (!out) return fail(DQ_ERR_INVALID, "NULL argument");
+  if (a->ctx->device != b->ctx->device) return fail(DQ_ERR_INVALID, "tables live on different devices");
+  if (a->ks.n_keys != b->ks.n_keys || a->ks.null_as_key != b->ks.null_as_key)
+    return fail(DQ_ERR_INVALID, "tables group different keys");
+  for (int i = 0; i < a->ks.n_keys; ++i)
+    if (a->col_types[a->ks.key_cols[i]] != b->col_types[b->ks.key_cols[i]])
+      return fail(DQ_ERR_INVALID, "tables group different key types");
+  DQ_HIP(hipSetDevice(a->ctx->device));
+  DQ_TRY(a->materialize());
+  if (b != a) DQ_TRY(b->materialize());
+  unsigned long long ha[FC_COUNT], hb[FC_COUNT];
+  DQ_TRY(a->read_counters(ha));
+  DQ_TRY(b->read_counters(hb));  // (also: b's stream is idle before a's kernels read its table)
+  DQ_TRY(a->d_dist.ensure(8 * sizeof(unsigned long long)));
+  unsigned long long* d = static_cast<unsigned long long*>(a->d_dist.ptr);
+  unsigned long long w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  DQ_HIP(hipMemsetAsync(d, 0, sizeof(w), a->stream));
+  if (ha[FC_GROUPS]) DQ_HIP(launch_freq_totals(a->view(), d + 2, a->stream));
+  if (hb[FC_GROUPS]) DQ_HIP(launch_freq_totals(b->view(), d + 5, a->stream));
+  if (ha[FC_GROUPS] || hb[FC_GROUPS]) {
+    DQ_HIP(hipMemcpyAsync(w, d, sizeof(w), hipMemcpyDeviceToHost, a->stream));
+    DQ_HIP(hipStreamSynchronize(a->stream));
+  }
+  const unsigned __int128 limit = (unsigned __int128)1 << 53;
+  const unsigned __int128 n = ((unsigned __int128)w[3] << 32) + w[2], m = ((unsigned __int128)w[6] << 32) + w[5];
+  if (n > limit || m > limit)
+    return fail(DQ_ERR_UNSUPPORTED, "a table's total count is above 2^53: its fp64 sum depends on the order of addition");
+  dq_freq_distance r{};
+  r.n = (int64_t)n;
+  r.m = (int64_t)m;
+  r.groups_a = (int64_t)w[4];
+  r.groups_b = (int64_t)w[7];
+  if (r.groups_a == 0 || r.groups_b == 0) {  // 0L / 0.0 on the empty side: NaN for every key there is
+    r.linf_simple = r.groups_a == 0 && r.groups_b == 0 ? 0.0 : std::numeric_limits<double>::quiet_NaN();
+    *out = r;
+    return DQ_OK;
+  }
+  unsigned long long res[2];
+  DQ_HIP(launch_freq_linf(a->view(), b->view(), (double)r.n, (double)r.m, d, d + 1, a->stream));
+  DQ_HIP(hipMemcpyAsync(res, d, sizeof(res), hipMemcpyDeviceToHost, a->stream));
+  DQ_HIP(hipStreamSynchronize(a->stream));
+  r.groups_common = (int64_t)res[1];
+  if (r.groups_common < r.groups_b) {  // keys only in b
+    DQ_HIP(launch_freq_linf(b->view(), a->view(), (double)r.m, (double)r.n, d, nullptr, a->stream));
+    DQ_HIP(hipMemcpyAsync(res, d, sizeof(unsigned long long), hipMemcpyDeviceToHost, a->stream));
+    DQ_HIP(hipStreamSynchronize(a->stream));
+  }
+  std::memcpy(&r.linf_simple, &res[0], sizeof(double));
+  if (r.n == 0 || r.m == 0) r.linf_simple = std::numeric_limits<double>::quiet_NaN();  // (groups of count 0 only)
+  *out = r;
   return DQ_OK;
 }
 

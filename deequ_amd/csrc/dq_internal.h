@@ -383,6 +383,14 @@ hipError_t launch_freq_hash(const uint64_t* d_k0, const uint64_t* d_k1, const ui
                             hipStream_t stream);
 hipError_t launch_freq_lookup(const FreqTable& T, const uint8_t* d_key, uint32_t len, unsigned long long* d_out,
                               hipStream_t stream, const FreqCompact* cmp = nullptr);
+// Distance (dq_freq_linf_distance, dq_freq.hip "Distance"): d_tot[0..3) += {sum of the counts' low
+// 32 bits, sum of their high 32 bits, occupied slots} of T's slot image; then one directed pass:
+// every group of X probes Y, *d_max = max(*d_max, bits of |cx / nx - cy / ny|) and *d_common
+// (nullptr: not counted) += the probes that hit.
+constexpr unsigned kFreqDistMaxBlocks = 2048;  // the passes' grid cap (kBlock slots per workgroup and trip)
+hipError_t launch_freq_totals(const FreqTable& T, unsigned long long* d_tot, hipStream_t stream);
+hipError_t launch_freq_linf(const FreqTable& X, const FreqTable& Y, double nx, double ny, unsigned long long* d_max,
+                            unsigned long long* d_common, hipStream_t stream);
 hipError_t launch_freq_heap_need(const FreqKeySpec& ks, const DevColumn* d_cols, int64_t n_rows,
                                  unsigned long long* d_need, unsigned long long* d_max_len, hipStream_t stream);
 // Sorted-bucket path (dq_freq.hip): stage rows as FreqRec + an HLL sketch of their hashes (to size

@@ -311,6 +311,13 @@ class FrequencyTable:
         """self += other, device to device."""
         L.check(L.lib().dq_freq_merge(self.handle, other.handle))
 
+    def linf_distance(self, other: "FrequencyTable") -> L.DqFreqDistance:
+        """The L-infinity distance of the two tables' relative frequencies with both totals and
+        the group counts (dq_freq_linf_distance), device to device; neither table changes."""
+        out = L.DqFreqDistance()
+        L.check(L.lib().dq_freq_linf_distance(self.handle, other.handle, ctypes.byref(out)))
+        return out
+
     def close(self) -> None:
         if getattr(self, "handle", None):
             L.lib().dq_freq_destroy(self.handle)

@@ -23,7 +23,7 @@ from __future__ import annotations
 import ctypes
 import math
 import struct
-from typing import List, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 from . import _lib as L
 
@@ -487,12 +487,45 @@ class QuantileNonSample:
     def _output(self):
         return [(v, 1 << i) for i, c in enumerate(self.compactors[:self.curNumOfCompactors]) for v in c.buffer]
 
-    def getRank(self, item: float) -> int:
-        """Weight of the items not greater than `item` (:163-171; Ordering.Double.gt is `>`)."""
+    def getRank(self, item: float, rankMap: Optional[Dict[float, int]] = None) -> int:
+        """Weight of the items not greater than `item` (:163-171; Ordering.Double.gt is `>`).
+        With `rankMap` (getRankMap's result) the reference's second overload (:194-205): the rank
+        of the last entry before the first one greater than `item`."""
+        if rankMap is not None:
+            cur = 0
+            for v, r in rankMap.items():
+                if v > item:
+                    break
+                cur = r
+            return cur
         return sum(w for v, w in self._output() if not v > item)
 
     def getRankExclusive(self, item: float) -> int:
         return sum(w for v, w in self._output() if v < item)
+
+    def getRankMap(self) -> Dict[float, int]:
+        """Item -> running rank, ascending by item (:126-139).  The reference first puts the
+        sorted (item, weight) pairs into a ListMap, which keeps one entry per item -- the last of
+        several equal items, with its weight alone -- and only then accumulates the weights."""
+        last: Dict[float, int] = {}
+        for v, w in sorted(self._output(), key=lambda iw: _java_sort_key(iw[0])):
+            last.pop(v, None)  # (ListMap.updated: the entry moves to the end)
+            last[v] = w
+        ranks: Dict[float, int] = {}
+        running = 0
+        for v, w in last.items():
+            running += w
+            ranks[v] = running
+        return dict(sorted(ranks.items(), key=lambda iw: _java_sort_key(iw[0])))
+
+    def getCDF(self) -> List[Tuple[float, float]]:
+        """(item, rank / total weight) per entry of the rank map (:146-155)."""
+        rankMap = self.getRankMap()
+        if not rankMap:
+            raise ValueError("getCDF of an empty sketch (the reference's `last` of an empty map throws)")
+        total = float(list(rankMap.values())[-1])
+        return [(v, float(r) / total) for v, r in rankMap.items()]
+
 
     def merge(self, that: "QuantileNonSample") -> "QuantileNonSample":
         """:215-230.  Mutates and returns self, as the reference does."""

@@ -516,6 +516,18 @@ dq_status dq_freq_top(dq_freq* f, int n, dq_freq_group* groups, int64_t max_grou
 /* dst += src on the device (FrequenciesAndNumRows.sum, GroupingAnalyzers.scala:128-148): both
  * tables on one device, grouping the same key types; src is unchanged. */
 dq_status dq_freq_merge(dq_freq* dst, dq_freq* src);
+/* Distance.categoricalDistance over two states (Distance.scala:43-87): linf_simple = the maximum
+ * over the union of keys of |ca / n - cb / m| (an absent key counts 0; each quotient one fp64
+ * division), bit-equal to the reference.  Exactly one table without groups: NaN (0L / 0.0); both:
+ * 0.0.  The tables' preconditions are dq_freq_merge's (a == b is allowed: 0.0); a total above
+ * 2^53 is DQ_ERR_UNSUPPORTED (the reference's fp64 sum then depends on its order).  Neither
+ * table changes.  selectMetrics' robust variant is the caller's arithmetic on linf_simple, n, m. */
+typedef struct dq_freq_distance {
+  double  linf_simple;
+  int64_t n, m;             /* sums of the group counts of a and of b */
+  int64_t groups_a, groups_b, groups_common;
+} dq_freq_distance;
+dq_status dq_freq_linf_distance(dq_freq* a, dq_freq* b, dq_freq_distance* out);
 /* Merge groups (and `num_rows`) into the table: FrequenciesAndNumRows.sum. */
 /* Count of one group (0 if the key is absent), key in the encoded form above.  Used to fold a
  * literal "NullValue" string into Histogram's NULL bin when Histogram shares the frequency
