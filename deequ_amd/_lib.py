@@ -203,6 +203,7 @@ DIAG_SIGNATURES = {
     "dq_diag_decimal_to_double": (c_int, [c_uint64, c_int64, c_int32, POINTER(c_double), POINTER(c_int32)]),
     "dq_diag_decimal_bytes": (c_int, [c_uint64, c_int64, c_char_p, POINTER(c_int32)]),
     "dq_diag_plan_groups": (c_int, [c_void_p, POINTER(c_int64), c_int32, POINTER(c_int32), POINTER(c_int64)]),
+    "dq_diag_plan_lanemask": (c_int, [c_void_p, POINTER(c_int32), c_int32, POINTER(c_int32)]),
 }
 
 
@@ -371,6 +372,16 @@ def diag_plan_groups(plan_handle):
     info = dict(zip(PLAN_LAUNCHES, launches[:7]))
     info.update(rows=launches[7], dec_per_cu=launches[8], n_cu=launches[9])
     return out, info
+
+
+def diag_plan_lanemask(plan_handle):
+    """dq_diag_plan_lanemask of a dq_plan: per scan task of the last consumed batch, True where
+    the fast scan's lane-mask loop ran (False for tasks of the other kernels)."""
+    n = ctypes.c_int32(0)
+    check(lib().dq_diag_plan_lanemask(plan_handle, None, 0, ctypes.byref(n)))
+    tasks = (c_int32 * max(1, n.value))()
+    check(lib().dq_diag_plan_lanemask(plan_handle, tasks, n.value, ctypes.byref(n)))
+    return [bool(tasks[t]) for t in range(n.value)]
 
 
 REGEX_MODES = {"find_non_empty": 0, "find": 1, "full": 2}

@@ -926,6 +926,8 @@ struct dq_plan : Stager {
   int n_cu = 0;          // compute units of the device (0 = unknown)
   int scan_rounds = 6;   // value-scan grids: whole rounds of resident workgroups (DQ_SCAN_ROUNDS)
   int max_blocks = 0;    // test hook: cap on every launch's blocks per task (DQ_SCAN_MAX_BLOCKS; 0 = none)
+  int lanemask_mode = 1;  // the fast scan's lane-mask loop (DQ_SCAN_LANEMASK: 0 off, 1 default, 2 every variant)
+  std::vector<int32_t> diag_task_lanemask;  // per scan task, the last batch: 1 = it ran the lane-mask loop
   // the last consumed batch's grids, for dq_diag_plan_groups (host bookkeeping only)
   std::vector<int64_t> diag_group_bpt;
   int64_t diag_launch_bpt[7] = {0, 0, 0, 0, 0, 0, 0};  // regex, string pass, hll, datatype, strlen, corr, dec
@@ -1422,6 +1424,7 @@ extern "C" dq_status dq_plan_create(dq_ctx* ctx, const dq_op* ops, int n_ops,
   }
   if (const char* r = std::getenv("DQ_SCAN_ROUNDS")) plan->scan_rounds = std::max(0, std::atoi(r));
   if (const char* r = std::getenv("DQ_SCAN_MAX_BLOCKS")) plan->max_blocks = std::max(0, std::atoi(r));
+  if (const char* r = std::getenv("DQ_SCAN_LANEMASK")) plan->lanemask_mode = std::min(2, std::max(0, std::atoi(r)));
   if ((s = dq_plan_reset(plan)) != DQ_OK) {
     delete plan;
     return s;
@@ -1455,6 +1458,16 @@ extern "C" dq_status dq_diag_plan_groups(dq_plan* plan, int64_t* groups, int32_t
   launches[7] = ran ? plan->diag_rows : 0;
   launches[8] = plan->dec_per_cu > 0 ? plan->dec_per_cu : 0;
   launches[9] = plan->n_cu;
+  return DQ_OK;
+}
+
+extern "C" dq_status dq_diag_plan_lanemask(dq_plan* plan, int32_t* tasks, int32_t capacity, int32_t* n_tasks) {
+  if (!plan || !n_tasks || capacity < 0 || (capacity > 0 && !tasks))
+    return fail(DQ_ERR_INVALID, "dq_diag_plan_lanemask: NULL argument");
+  *n_tasks = (int32_t)plan->scan_tasks.size();
+  const bool ran = plan->diag_task_lanemask.size() == plan->scan_tasks.size() && plan->diag_rows > 0;
+  for (size_t t = 0; t < plan->scan_tasks.size() && (int32_t)t < capacity; ++t)
+    tasks[t] = ran ? plan->diag_task_lanemask[t] : 0;
   return DQ_OK;
 }
 
@@ -1695,6 +1708,7 @@ extern "C" dq_status dq_plan_consume(dq_plan* plan, const dq_column* columns, in
     part_total += bpt * ng;
   }
   plan->diag_group_bpt = group_bpt;
+  plan->diag_task_lanemask.assign((size_t)n_scan, 0);
   for (int64_t& b : plan->diag_launch_bpt) b = 0;
   plan->diag_rows = n_rows;
   if (n_scan > 0) DQ_TRY(plan->d_partials.ensure((size_t)part_total * sizeof(ScanAcc)));
@@ -1759,11 +1773,14 @@ extern "C" dq_status dq_plan_consume(dq_plan* plan, const dq_column* columns, in
     const int32_t* d_groups = static_cast<const int32_t*>(plan->d_groups.ptr);
     for (size_t g = 0; g < plan->groups.size(); ++g) {
       const ScanGroup& G = plan->groups[g];
-      if (G.kind == 2)
+      if (G.kind == 2) {
+        const bool lanemask = scan_fast_lanemask_variant(plan->lanemask_mode, G.np);
+        for (int32_t t : G.tasks)  // what each block of the task decides from its column's bitmap
+          plan->diag_task_lanemask[t] = scan_fast_lanemask(lanemask, h_cols[plan->scan_tasks[t].primary].validity);
         DQ_HIP(launch_scan_fast(G.ptype, G.np, d_tasks, d_groups + G.dev_offset, (int)G.tasks.size(), d_cols, n_rows,
                                 (int)group_bpt[g], parts + group_base[g], static_cast<uint32_t*>(plan->d_regs.ptr),
-                                plan->stream));
-      else
+                                lanemask, plan->stream));
+      } else
         DQ_HIP(launch_scan_group(G.kind, G.ptype, G.np, d_tasks, d_groups + G.dev_offset, (int)G.tasks.size(),
                                  d_cols, d_masks, n_rows, (int)group_bpt[g], parts + group_base[g],
                                  static_cast<uint32_t*>(plan->d_regs.ptr), plan->stream));

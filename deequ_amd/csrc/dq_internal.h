@@ -534,8 +534,22 @@ constexpr int FAST_STATS = 8;
 constexpr int FAST_HLL = 16;
 hipError_t launch_scan_fast(int ptype, int variant, const ScanTask* d_tasks, const int32_t* d_group, int n_group,
                             const DevColumn* d_cols, int64_t n_rows, int blocks_per_task, ScanAcc* d_partials,
-                            uint32_t* d_hll_regs, hipStream_t stream);
+                            uint32_t* d_hll_regs, bool lanemask, hipStream_t stream);
 int scan_fast_blocks_per_cu(int ptype, int variant);  // 0 = unknown
+// Whether a task of a launch with `lanemask` set runs the lane-mask loop: it reads the validity
+// words with scalar loads, which want a 4-byte aligned bitmap (or none).  One rule for the kernel
+// and for the host's bookkeeping (dq_diag_plan_lanemask).
+__host__ __device__ inline bool scan_fast_lanemask(bool lanemask, const uint8_t* validity) {
+  return lanemask && (reinterpret_cast<uintptr_t>(validity) & 3u) == 0u;
+}
+// The launch's `lanemask` for a fast variant under DQ_SCAN_LANEMASK (mode 0 off, 1 default, 2 every
+// variant): by default the variants with HLL, which are bound by VALU issue.  The ones without
+// run close to the memory bound: with the loop the 57-analyzer statistics pass measured 10.31
+// against 10.39 ms, inside the A/B's noise bar, and the predicate-only tasks ran slower
+// (DESIGN.md §5), so they keep the stand-in loop.
+inline bool scan_fast_lanemask_variant(int mode, int variant) {
+  return mode >= 2 || (mode == 1 && (variant & FAST_HLL) != 0);
+}
 hipError_t launch_diag_hash(int blocks, int iters, bool with_hll, uint64_t* sink, hipStream_t s);
 int scan_group_blocks_per_cu(int kind, int ptype, int np);  // 0 = unknown
 hipError_t launch_scan_reduce(const ScanAcc* d_partials, const PartRange* d_ranges, int n_tasks,

@@ -10,8 +10,18 @@
 // by HBM.  Measured on gfx950 (tools/ubench/valu_rates.hip, 8 waves per SIMD), a wave64 VALU
 // instruction costs the SIMD ~2.3 cycles for add/sub/and/or/xor/lshr/bitop3/fma_f32 and ~4.2
 // for nearly everything else (64-bit ops, multiplies, alignbit, compares, conversions,
-// cndmask).  So this kernel is written for the fewest *weighted* issue cycles per row:
-//   * NULL rows are neutralised once, not per statistic: a row that is not selected takes the
+// cndmask).  So this kernel is written for the fewest *weighted* issue cycles per row.
+//
+// Two main loops share the kernel, its partials and its epilogue; a block picks one from its
+// task's bitmap (scan_fast_lanemask, dq_internal.h) and the launch's `lanemask` flag:
+//   * the lane-mask loop (lm_main_loop, further down; the variants with HLL by default) maps rows
+//     to lanes so that a 64-bit validity word is a wave's lane mask, read on the scalar unit: a
+//     NULL row costs no VALU instruction (46.7 / 47.4 VALU instructions per int64 / fp64 value row
+//     against 51.0 / 51.2, C2 12.95 against 13.55 ms on one box) and needs no stand-in value;
+//   * the stand-in loop (fast_main_loop) serves a bitmap that is not 4-byte aligned, the variants
+//     without HLL, and DQ_SCAN_LANEMASK=0.  It is the form the next bullet describes.
+// Common to both, unless the bullet says otherwise:
+//   * (stand-in loop) NULL rows are neutralised once, not per statistic: an unselected row takes the
 //     wave's shift value c (the first valid value the wave saw) through ONE bitop3 per 32-bit
 //     word, `xm = valid ? x : c`.  c is itself a selected value of the column, so
 //       - Min / Max and the HLL registers are unchanged by extra copies of c (min, max and the
@@ -233,6 +243,10 @@ typedef uint32_t v4u __attribute__((ext_vector_type(4)));
 #define DQ_VALID_AUX 0
 #endif
 constexpr int kFastUnroll = DQ_FAST_UNROLL;  // 16-byte loads (2 rows) per lane per iteration
+#ifndef DQ_LM_HASH_GROUP
+#define DQ_LM_HASH_GROUP 4
+#endif
+constexpr int kLmHashGroup = DQ_LM_HASH_GROUP;  // lane-mask loop: hashes whose keys are held at once
 
 // Streaming loads of a large pass go non-temporal (aux = 2: the bytes are read once and are far
 // larger than the 256 MiB Infinity Cache; A/B 13.11 vs 13.22 ms on C2); a small table (C1's 10M
@@ -377,6 +391,225 @@ __device__ inline void fast_tail(FastAcc& a, __amdgpu_buffer_rsrc_t rv, __amdgpu
   if constexpr (__is_same(T, double) && STATS) neumaier_add(a.fs, a.fc, dsum);
 }
 
+// ----------------------------------------------------------------------------- the lane-mask loop
+// The same pass with the row-to-lane mapping turned so that a 64-bit word of the validity bitmap
+// IS a wave's lane mask: wave w of the block owns rows it * 2048 + w * 512 + u * 64 + lane
+// (u = 0..7), eight 8-byte loads per lane per iteration, and reads its 512 validity bits with ONE
+// 64-byte load on the scalar unit.  A row's mask then costs no VALU instruction at all:
+//   * the selected rows are counted with s_bcnt1 of the word;
+//   * the statistics and the register update of a row run under `if (inverse_ballot(word))`, i.e.
+//     with the word as EXEC (s_and_saveexec from SGPRs): a NULL row is simply not executed, so
+//     there is no stand-in value, no select per 32-bit half, no MEMBER / masked split and no
+//     end-of-wave correction of the sum, the predicate count or the fp64 sum;
+//   * the hash runs under full EXEC on the raw halves (a NULL row's garbage is hashed and dropped);
+//   * the predicate is one v_cmp under full EXEC whose mask is and-ed with the word on the scalar
+//     unit before the s_bcnt1.
+// The scalar load has no descriptor range check and wants a 4-byte aligned address, so the host
+// selects this loop per task only for such a bitmap (or none), and a mask load is issued only for
+// an iteration that exists (a full iteration's 256 validity bytes lie wholly inside the bitmap's
+// (n + 7) / 8 bytes).
+typedef uint32_t v2u __attribute__((ext_vector_type(2)));
+typedef uint32_t lm_words __attribute__((ext_vector_type(16), aligned(4)));
+constexpr int kLmRows = 8;  // rows per lane per iteration: 4 waves x 8 x 64 = 2048 rows per block
+
+struct LmLoad {
+  v2u v[kLmRows];
+};
+struct LmMasks {
+  uint64_t m[kLmRows];
+};
+
+template <int AUX>
+__device__ inline void lm_load_aux(LmLoad& L, __amdgpu_buffer_rsrc_t rv, uint32_t it) {
+  const uint32_t tid = threadIdx.x;
+  // (a load past the chunk -- the look-ahead -- reads 0 through the descriptor's range check)
+  const uint32_t r0 = it * ((uint32_t)kBlock * kLmRows) + (tid >> 6) * (64u * kLmRows) + (tid & 63u);
+#pragma unroll
+  for (int u = 0; u < kLmRows; ++u)
+    L.v[u] = __builtin_amdgcn_raw_buffer_load_b64(rv, (int)((r0 + (uint32_t)u * 64u) * 8u), 0, AUX);
+}
+__device__ inline void lm_load(LmLoad& L, __amdgpu_buffer_rsrc_t rv, uint32_t it, bool nt) {
+  if (nt) lm_load_aux<2>(L, rv, it);  // (wave-uniform)
+  else lm_load_aux<0>(L, rv, it);
+}
+
+// The wave's eight mask words at byte `off` (wave-uniform) of the chunk's bitmap: one scalar
+// load through the constant address space, default cache policy.  No bitmap: all ones.
+__device__ inline void lm_load_masks(LmMasks& M, const uint8_t* vbase, uint32_t off) {
+  if (vbase) {
+    const lm_words w = *(const __attribute__((address_space(4))) lm_words*)(vbase + off);
+#pragma unroll
+    for (int u = 0; u < kLmRows; ++u) M.m[u] = ((uint64_t)w[2 * u + 1] << 32) | w[2 * u];
+  } else {
+#pragma unroll
+    for (int u = 0; u < kLmRows; ++u) M.m[u] = ~0ull;
+  }
+}
+
+template <typename T, int PK>
+__device__ inline bool fast_pred(uint32_t lo, uint32_t hi, int64_t lit_i, double lit_f) {
+  constexpr bool INT = !__is_same(T, double);
+  if constexpr (PK == PK_LT_I) return (int64_t)(((uint64_t)hi << 32) | lo) < lit_i;
+  else if constexpr (PK == PK_EQ_I) return (int64_t)(((uint64_t)hi << 32) | lo) == lit_i;
+  else {
+    const double xd = INT ? i64_to_f64(lo, hi) : __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+    if constexpr (PK == PK_LT_F) return xd < lit_f;
+    else return xd == lit_f;
+  }
+}
+
+// One iteration: `sel` (wave-uniform, SGPR) counts the selected rows, a.pc the selected rows the
+// comparison holds for.  The iteration's mask words are loaded here, at its top, into the ONE set
+// of 16 SGPRs the kernel can afford (a second set for a look-ahead spilled SGPRs into the loop):
+// with HLL the hashes of the first group of rows, which need no mask, run before the first use
+// and cover the load.
+template <typename T, int PK, bool STATS, bool HLL>
+__device__ inline void lm_compute(FastAcc& a, uint32_t& sel, const LmLoad& L, const uint8_t* vbase, uint32_t voff,
+                                  double shift, double cshift, int64_t lit_i, double lit_f, uint32_t* lregs,
+                                  uint32_t* s_nan) {
+  constexpr bool FP = __is_same(T, double);
+  constexpr int G = kLmHashGroup;
+  LmMasks M;
+  lm_load_masks(M, vbase, voff);
+  uint32_t koff[G], ks[G];
+  if constexpr (HLL) {
+#pragma unroll
+    for (int k = 0; k < G; ++k) hll_key_min(hash_halves<T>(L.v[k][0], L.v[k][1]), koff[k], ks[k]);
+    __builtin_amdgcn_sched_barrier(0);  // (no use of a mask word, i.e. its wait, moves above the hashes)
+  }
+  double dsum = -0.0;
+  // statistics + predicate of all rows before the register updates: for fp64 the iteration's Σx
+  // tells whether a selected NaN is present (it would be NaN), which the hash needs to know
+  // (the compares in one block of their own: placed between the masked regions, the block
+  // layout duplicates them into both successors of every region)
+#pragma unroll
+  for (int u = 0; u < kLmRows; ++u) {
+    sel += (uint32_t)__builtin_popcountll(M.m[u]);
+    if constexpr (PK != PK_NONE)
+      a.pc += __builtin_popcountll(__ballot(fast_pred<T, PK>(L.v[u][0], L.v[u][1], lit_i, lit_f)) & M.m[u]);
+  }
+#pragma unroll
+  for (int u = 0; u < kLmRows; ++u) {
+    if constexpr (STATS) {
+      if (__builtin_expect(__builtin_amdgcn_inverse_ballot_w64(M.m[u]), 1))  // (laid out as the fall-through)
+        fast_row<T, PK_NONE, true, false, true>(a, L.v[u][0], L.v[u][1], ~0u, shift, cshift, dsum, lit_i, lit_f, lregs,
+                                                false);
+    }
+  }
+  bool nan_possible = false;
+  if constexpr (FP && !STATS && HLL) {  // no Σx to look at: one ordered compare per row (raw: a NULL
+    bool any = false;                   // row's NaN only costs the rare form of the hash loop)
+#pragma unroll
+    for (int u = 0; u < kLmRows; ++u) {
+      const double x = __builtin_bit_cast(double, ((uint64_t)L.v[u][1] << 32) | L.v[u][0]);
+      any = any || (x != x);
+    }
+    nan_possible = __ballot(any) != 0;
+  }
+  if constexpr (FP && STATS) {
+    nan_possible = __ballot(dsum != dsum) != 0;
+    if (nan_possible) {  // rare; the flag lives in LDS so this stays a branch
+#pragma unroll
+      for (int u = 0; u < kLmRows; ++u) {
+        const double x = __builtin_bit_cast(double, ((uint64_t)L.v[u][1] << 32) | L.v[u][0]);
+        if (((M.m[u] >> (threadIdx.x & 63u)) & 1u) && is_nan_rare(x)) *s_nan = 1u;
+      }
+    }
+    neumaier_add(a.fs, a.fc, dsum);
+  }
+  if constexpr (HLL) {
+    // the hashes of the raw halves under full EXEC (a NULL row's garbage is hashed and dropped),
+    // in groups whose keys stay in registers, then each row's ds_min under its mask
+#pragma unroll
+    for (int g = 0; g < kLmRows; g += G) {
+      if (FP && nan_possible) {  // wave-uniform and rare: Double.doubleToLongBits' canonical NaN
+#pragma unroll
+        for (int k = 0; k < G; ++k) {
+          uint32_t hlo = L.v[g + k][0], hhi = L.v[g + k][1];
+          if (is_nan_rare(__builtin_bit_cast(double, ((uint64_t)hhi << 32) | hlo))) {
+            hlo = 0u;
+            hhi = 0x7ff80000u;
+          }
+          hll_key_min(hash_halves<T>(hlo, hhi), koff[k], ks[k]);
+        }
+      } else if (g > 0) {  // (the first group's were taken above)
+#pragma unroll
+        for (int k = 0; k < G; ++k) hll_key_min(hash_halves<T>(L.v[g + k][0], L.v[g + k][1]), koff[k], ks[k]);
+      }
+#pragma unroll
+      for (int k = 0; k < G; ++k)
+        if (__builtin_expect(__builtin_amdgcn_inverse_ballot_w64(M.m[g + k]), 1)) lds_min(lregs, koff[k], ks[k]);
+    }
+  }
+}
+
+template <typename T, int PK, bool STATS, bool HLL>
+__device__ inline void lm_main_loop(FastAcc& a, uint32_t& sel, __amdgpu_buffer_rsrc_t rv, const uint8_t* vbase,
+                                    uint32_t full_iters, double shift, double cshift, int64_t lit_i, double lit_f,
+                                    uint32_t* lregs, uint32_t* s_nan, bool nt) {
+  // the same two-stage pipeline of the values as fast_main_loop (a mask load is only ever issued
+  // for an iteration that exists: it has no range check)
+  LmLoad A, B;
+  constexpr uint32_t ITER_BYTES = (uint32_t)kBlock * kLmRows / 8u;  // 256 validity bytes per iteration
+  const uint32_t woff = __builtin_amdgcn_readfirstlane((threadIdx.x >> 6) * (8u * kLmRows));
+  uint32_t it = 0;
+  if (full_iters > 0) lm_load(A, rv, 0, nt);
+#pragma unroll 1
+  for (; it + 1 < full_iters; it += 2) {
+    lm_load(B, rv, it + 1, nt);
+    lm_compute<T, PK, STATS, HLL>(a, sel, A, vbase, it * ITER_BYTES + woff, shift, cshift, lit_i, lit_f, lregs, s_nan);
+    lm_load(A, rv, it + 2, nt);
+    lm_compute<T, PK, STATS, HLL>(a, sel, B, vbase, (it + 1) * ITER_BYTES + woff, shift, cshift, lit_i, lit_f, lregs,
+                                  s_nan);
+  }
+  if (it < full_iters)
+    lm_compute<T, PK, STATS, HLL>(a, sel, A, vbase, it * ITER_BYTES + woff, shift, cshift, lit_i, lit_f, lregs, s_nan);
+  a.n_rows += full_iters * kLmRows;
+}
+
+// The ragged end of the chunk for the lane-mask loop: one row per lane, a NULL row not executed
+// either (no stand-in anywhere in this form, so the epilogue has nothing to take back out).
+// a.n_sel counts the lane's selected tail rows.
+template <typename T, int PK, bool STATS, bool HLL>
+__device__ inline void lm_tail(FastAcc& a, __amdgpu_buffer_rsrc_t rv, __amdgpu_buffer_rsrc_t rvalid, uint32_t no_valid,
+                               uint32_t first, uint32_t span, double shift, double cshift, int64_t lit_i,
+                               double lit_f, uint32_t* lregs, uint32_t* s_nan) {
+  double dsum = 0.0;
+  for (uint32_t r = first + threadIdx.x; r < span; r += kBlock) {
+    const auto v = __builtin_amdgcn_raw_buffer_load_b64(rv, (int)(r * 8u), 0, 0);
+    const uint32_t bit = (((uint32_t)__builtin_amdgcn_raw_buffer_load_b8(rvalid, (int)(r >> 3), 0, 0) | no_valid) >>
+                          (r & 7u)) & 1u;
+    const uint32_t lo = (uint32_t)v[0], hi = (uint32_t)v[1];
+    a.n_sel += bit;
+    a.n_rows += 1;
+    // (lane 0 of a wave is in the loop whenever any of its lanes is, and it carries a.pc)
+    if constexpr (PK != PK_NONE)
+      a.pc += __builtin_popcountll(__ballot(bit != 0u && fast_pred<T, PK>(lo, hi, lit_i, lit_f)));
+    if (bit) {
+      fast_row<T, PK_NONE, STATS, false, true>(a, lo, hi, ~0u, shift, cshift, dsum, lit_i, lit_f, lregs, false);
+      if constexpr (__is_same(T, double) && STATS) {
+        const double x = __builtin_bit_cast(double, ((uint64_t)hi << 32) | lo);
+        if (x != x) *s_nan = 1u;
+      }
+      if constexpr (HLL) {
+        double unused = 0.0;
+        fast_row<T, PK_NONE, false, true, true>(a, lo, hi, ~0u, shift, cshift, unused, lit_i, lit_f, lregs, true);
+      }
+    }
+  }
+  if constexpr (__is_same(T, double) && STATS) neumaier_add(a.fs, a.fc, dsum);
+}
+
+// Σ over the wave of the lanes' int64 sums as a 128-bit integer, less n * c, rounded to double
+// once (lane 0).  Each lane's v must be its true sum (no wrap): the caller's guard.
+__device__ inline double lm_wave_sum_less(int64_t v, uint64_t n, int64_t c) {
+  const uint64_t lo = wave_sum_u64((uint64_t)v & 0xffffffffull);
+  const int64_t hi = (int64_t)wave_sum_u64((uint64_t)(v >> 32));
+  const __int128 t = (((__int128)hi) << 32) + (__int128)lo - (__int128)n * (__int128)c;
+  const int64_t th = (int64_t)(t >> 32);
+  return fma((double)th, 0x1p32, (double)(uint32_t)t);
+}
+
 __device__ inline void fast_acc_init(FastAcc& a) {
   a.n_sel = a.n_rows = 0u;
   a.isum = 0u;
@@ -403,7 +636,8 @@ template <typename T, int PK, bool STATS, bool HLL>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DQ_FAST_WAVES))) void dq_scan_fast_kernel(const ScanTask* __restrict__ tasks,
                                                               const int32_t* __restrict__ group,
                                                               const DevColumn* __restrict__ cols, int64_t n_rows,
-                                                              ScanAcc* partials, uint32_t* __restrict__ hll_regs) {
+                                                              ScanAcc* partials, uint32_t* __restrict__ hll_regs,
+                                                              uint32_t lanemask) {
   constexpr bool FP = __is_same(T, double);
   constexpr bool INT_STATS = !FP && STATS;
   const ScanTask& task = tasks[group[blockIdx.y]];
@@ -423,6 +657,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DQ_FAST_
   const __amdgpu_buffer_rsrc_t rv = make_rsrc(static_cast<const uint64_t*>(col.values) + row_begin, span * 8u);
   const bool has_valid = col.validity != nullptr;
   const uint32_t no_valid = has_valid ? 0u : 0xffu;
+  // block-uniform, and the same rule the host reports through dq_diag_plan_lanemask
+  const bool lm = scan_fast_lanemask(lanemask != 0u, col.validity);
   const __amdgpu_buffer_rsrc_t rvalid =
       make_rsrc(has_valid ? col.validity + (row_begin >> 3) : nullptr, has_valid ? (span + 7u) >> 3 : 0u);
   int64_t lit_i = 0;
@@ -492,7 +728,13 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DQ_FAST_
   fast_acc_init(a);
   constexpr uint32_t ROWS_PER_ITER = (uint32_t)kBlock * 2u * kFastUnroll;
   const uint32_t full_iters = span / ROWS_PER_ITER;
-  if (member) {
+  uint32_t sel_main = 0u;  // lane-mask loop: the wave's selected rows of the full iterations (SGPR)
+  if (lm) {  // c = 0 where the probe found none: nothing stands in for a NULL row in this form
+    lm_main_loop<T, PK, STATS, HLL>(a, sel_main, rv, has_valid ? col.validity + (row_begin >> 3) : nullptr, full_iters,
+                                    shift, cshift, lit_i, lit_f, lregs, &s_nan, nt);
+    lm_tail<T, PK, STATS, HLL>(a, rv, rvalid, no_valid, full_iters * ROWS_PER_ITER, span, shift, cshift, lit_i, lit_f,
+                               lregs, &s_nan);
+  } else if (member) {
     fast_main_loop<T, PK, STATS, HLL, true>(a, rv, rvalid, no_valid, full_iters, sh_lo, sh_hi, shift, cshift, lit_i,
                                             lit_f, lregs, &s_nan, nt);
     fast_tail<T, PK, STATS, HLL, true>(a, rv, rvalid, no_valid, full_iters * ROWS_PER_ITER, span, sh_lo, sh_hi,
@@ -512,7 +754,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DQ_FAST_
   uint32_t mom_sel = a.n_sel;  // the lane's selected rows behind Σd, Σd² (the re-run visits other rows)
   if constexpr (INT_STATS) {
     const double dmax = (a.fmin <= a.fmax) ? fmax(fabs(a.fmin), fabs(a.fmax)) : 0.0;
-    const bool bad = a.n_rows > 0 && (dmax >= 0x1p50 || dmax * (double)a.n_rows >= 0x1p62 || a.s2 != a.s2);
+    // (lane-mask loop: Σd is rebuilt per wave from the lanes' sums of x themselves, so those must
+    // not have wrapped: |x| <= |d| + |c| with |c| < 2^50)
+    const bool bad = a.n_rows > 0 && (dmax >= 0x1p50 || (dmax + (lm ? 0x1p50 : 0.0)) * (double)a.n_rows >= 0x1p62 ||
+                                      a.s2 != a.s2);
     if (__syncthreads_or(bad)) {
       DQ_SCAN_COUNT(0);
       exact_stats = true;
@@ -534,9 +779,13 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DQ_FAST_
       // back to x: min / max of the selected values, Σd of the lane
       a.fmin = a.fmin + shift;
       a.fmax = a.fmax + shift;
-      a.s1 = (double)(int64_t)(a.isum - (uint64_t)a.n_rows * (((uint64_t)sh_hi << 32) | sh_lo));
+      // (lane-mask loop: a lane does not know how many of its rows were selected; S1 below)
+      a.s1 = lm ? 0.0 : (double)(int64_t)(a.isum - (uint64_t)a.n_rows * (((uint64_t)sh_hi << 32) | sh_lo));
     }
   }
+  // lane-mask loop: the wave's selected rows (valid in lane 0) = the scalar count of the full
+  // iterations + the lanes' tail rows
+  const uint64_t sel_lm = lm ? wave_sum_u64(a.n_sel) + sel_main : 0u;
 
   // The moments' cancellation guard (moments_cancel, dq_scan_common.h): a wave whose shift was an
   // outlier makes the workgroup redo Σd, Σd² of its chunk about the chunk's mean.  The re-run's
@@ -550,6 +799,12 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DQ_FAST_
     mom_w = wave_sum_u64(mom_sel);
     S1 = wave_sum_f64(a.s1);
     S2 = wave_sum_f64(a.s2);
+    if (lm && !exact_stats) {
+      mom_w = sel_lm;
+      // int64: Σd = Σx - n·c exactly, over the whole wave (fp64 summed d itself under the mask)
+      if constexpr (INT_STATS)
+        S1 = lm_wave_sum_less((int64_t)a.isum, sel_lm, (int64_t)(((uint64_t)sh_hi << 32) | sh_lo));
+    }
     double wn = 0.0, wmean = 0.0;
     bool cancel = false;
     if (lane0 && mom_w > 0) {
@@ -633,8 +888,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DQ_FAST_
   // ---- lane accumulators -> the block's ScanAcc partial (same layout as dq_scan_values_kernel;
   // block_reduce_store sums / merges the lanes, so lane 0 carries the wave-level terms)
   const uint64_t rows_w = wave_sum_u64(a.n_rows);  // lane 0
-  const uint64_t sel_w = wave_sum_u64(a.n_sel);    // lane 0
-  const uint64_t unsel_w = rows_w - sel_w;
+  const uint64_t sel_w = lm ? sel_lm : wave_sum_u64(a.n_sel);  // lane 0
+  // the rows a stand-in was accumulated for: none in the lane-mask loop, whose sums, predicate
+  // count and fp64 sum therefore take none of the corrections below
+  const uint64_t unsel_w = lm ? 0u : rows_w - sel_w;
   const uint64_t sh_bits = ((uint64_t)sh_hi << 32) | sh_lo;
   uint64_t isum = 0u;
   double mean = 0.0, m2 = 0.0, fs = 0.0, fc = 0.0;
@@ -643,7 +900,9 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DQ_FAST_
     fs = a.fs;
     fc = a.fc;
     if (lane0) {
-      if constexpr (!FP) isum -= unsel_w * sh_bits;  // the stand-in copies of unselected rows (wrapping)
+      if constexpr (!FP) {
+        if (!lm) isum -= unsel_w * sh_bits;  // the stand-in copies of unselected rows (wrapping)
+      }
       if (mom_w > 0) {
         const double n = (double)mom_w;
         mean = mom_shift + S1 / n;
@@ -651,7 +910,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DQ_FAST_
         m2 = (m2 < 0.0) ? 0.0 : m2;  // rounding; NaN/Inf propagate
       }
       if constexpr (FP) {  // the stand-in copies out of Σx: - n_unsel * c, its rounding kept by an fma
-        if (unsel_w > 0) {
+        if (!lm && unsel_w > 0) {
           const double u = (double)unsel_w;
           const double p = u * shift;
           const double pe = (p - p == 0.0) ? fma(u, shift, -p) : 0.0;
@@ -668,8 +927,13 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(DQ_FAST_
       else if constexpr (PK == PK_EQ_I) pc_shift = (int64_t)sh_bits == lit_i;
       else if constexpr (PK == PK_LT_F) pc_shift = shift < lit_f;
       else pc_shift = shift == lit_f;
-      uint64_t c_all = inv ? rows_w - a.pc : a.pc;
-      if (pc_shift != inv) c_all -= unsel_w;
+      uint64_t c_all;
+      if (lm) {  // a.pc counted selected rows only
+        c_all = inv ? sel_w - a.pc : a.pc;
+      } else {
+        c_all = inv ? rows_w - a.pc : a.pc;
+        if (pc_shift != inv) c_all -= unsel_w;
+      }
       pm[0] = c_all;
       pn[0] = sel_w;  // `column CMP literal` is NULL exactly when the column is
     }
@@ -717,11 +981,12 @@ static const void* fast_kernel_for(int ptype, int variant) {
 
 hipError_t launch_scan_fast(int ptype, int variant, const ScanTask* d_tasks, const int32_t* d_group, int n_group,
                             const DevColumn* d_cols, int64_t n_rows, int blocks_per_task, ScanAcc* d_partials,
-                            uint32_t* d_hll_regs, hipStream_t stream) {
+                            uint32_t* d_hll_regs, bool lanemask, hipStream_t stream) {
   if (n_group <= 0) return hipSuccess;
   const void* fn = fast_kernel_for(ptype, variant);
   if (!fn) return hipErrorInvalidValue;
-  void* args[] = {&d_tasks, &d_group, &d_cols, &n_rows, &d_partials, &d_hll_regs};
+  uint32_t lm_arg = lanemask ? 1u : 0u;
+  void* args[] = {&d_tasks, &d_group, &d_cols, &n_rows, &d_partials, &d_hll_regs, &lm_arg};
 #ifdef DQ_SCAN_DIAG
   {
     unsigned long long z[4] = {0, 0, 0, 0};

@@ -137,6 +137,14 @@ dq_status dq_diag_decimal_bytes(uint64_t lo, int64_t hi, uint8_t* out, int32_t* 
 dq_status dq_diag_plan_groups(dq_plan* plan, int64_t* groups, int32_t capacity, int32_t* n_groups,
                               int64_t* launches);
 
+/* Which scan tasks of the plan's last non-empty batch ran the lane-mask loop of dq_scan_fast_kernel
+ * (host bookkeeping, by the rule the kernel's blocks apply: the launch's variant takes the loop
+ * under DQ_SCAN_LANEMASK, and the task's column has no validity bitmap or a 4-byte aligned one).
+ * *n_tasks = the plan's scan tasks, in the order dq_diag_plan_groups' groups list them by index;
+ * for the first min(*n_tasks, capacity) of them tasks[t] = 1 or 0 (0 for a task of another kernel,
+ * and before the first batch). */
+dq_status dq_diag_plan_lanemask(dq_plan* plan, int32_t* tasks, int32_t capacity, int32_t* n_tasks);
+
 #ifdef __cplusplus
 }
 #endif
