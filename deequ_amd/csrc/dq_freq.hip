@@ -1512,10 +1512,6 @@ constexpr int kStagePer = DQ_STAGE_PER;   // rows per thread per fused-stage til
 #endif
 constexpr int kStageThreads = DQ_STAGE_NT;
 constexpr uint32_t kStageTile = (uint32_t)kStageThreads * kStagePer;
-#ifndef DQ_STAGEP_SUB
-#define DQ_STAGEP_SUB kStageTile
-#endif
-constexpr uint32_t kStageSubP = DQ_STAGEP_SUB;  // packed records per LDS round of the fused stage
 #ifndef DQ_STAGE_SUB16
 #define DQ_STAGE_SUB16 3072  // (2048: 33.3 ms per alnum C4 step, 3072: 32.4, 6144: 32.8 -- profiles/r06g_c4_alnum_stage_sub_ab.txt)
 #endif
@@ -1609,19 +1605,12 @@ __device__ unsigned long long g_stage_blk[4096][2];  // per workgroup: wall-cloc
 #define DQ_PROF_MARK(PROF, i) do { } while (0)
 #endif
 
-
-struct NoMid {
-  __device__ void operator()() const {}
-};
-// pre_res(): called as the tile's room is reserved (the fused stage reads its abort flag there).
-template <int PER, int MAXB, typename R, uint32_t SUBN, bool PROF = false, int WOUT_UNROLL = 0,
-          bool REC_LDS = false, int NT = kPartThreads, typename PreRes = NoMid>
+template <int PER, int MAXB, typename R, uint32_t SUBN, bool PROF = false, int WOUT_UNROLL = 0, int NT = kPartThreads>
 __device__ inline void part_tile(PartLdsT<MAXB, R, SUBN>& L, const R (&rec)[PER], uint32_t (&bin)[PER],
                                  uint32_t nb, uint64_t base_id, R* __restrict__ out, uint64_t out_cap,
                                  unsigned long long* out_fill, FreqRec* ovf, unsigned long long* ovf_n,
                                  uint64_t ovf_cap, unsigned int* flag, unsigned long long* staged,
-                                 const unsigned long long* region_start = nullptr, unsigned long long prof_t_ = 0,
-                                 const PreRes& pre_res = PreRes()) {
+                                 const unsigned long long* region_start = nullptr, unsigned long long prof_t_ = 0) {
   // region_start != nullptr: exact regions -- output region id starts at record region_start[id]
   // of `out` (sizes counted beforehand: nothing can overflow), out_fill is its cursor
   constexpr uint32_t SUB = SUBN;
@@ -1691,7 +1680,6 @@ __device__ inline void part_tile(PartLdsT<MAXB, R, SUBN>& L, const R (&rec)[PER]
   }
   lds_barrier();
   DQ_PROF_MARK(PROF, 4);
-  pre_res();  // (the fused stage's flag read: its latency overlaps the reservation atomics')
   // The tile's room in each bin's region: ONE device atomic per non-empty bin, issued here and
   // published to LDS only after the records are placed in the image, so the atomics' latency
   // overlaps that work.  Published per bin: gbase = the output index of tile position 0 (the
@@ -1726,15 +1714,6 @@ __device__ inline void part_tile(PartLdsT<MAXB, R, SUBN>& L, const R (&rec)[PER]
   };
   const uint32_t total = L.total;
   DQ_PROF_MARK(PROF, 5);
-  // REC_LDS: the caller left the records in L.rec in row order (record i of thread t at
-  // i * NT + t; registers are short while the keys load): read back, then sorted
-  R rl[PER];
-  if constexpr (REC_LDS) {
-    static_assert(SUB >= (uint32_t)PER * (uint32_t)NT, "a tile's records in one image");
-#pragma unroll
-    for (int i = 0; i < PER; ++i) rl[i] = L.rec[i * NT + t];
-    lds_barrier();
-  }
   for (uint32_t r0 = 0; r0 < total; r0 += SUB) {
 #pragma unroll
     for (int i = 0; i < PER; ++i) {
@@ -1742,7 +1721,7 @@ __device__ inline void part_tile(PartLdsT<MAXB, R, SUBN>& L, const R (&rec)[PER]
       const uint32_t b = bin[i] & 0xFFFFu;
       const uint32_t p = L.start[b] + (bin[i] >> 16) - r0;
       if (p < SUB) {
-        L.rec[p] = REC_LDS ? rl[i] : rec[i];
+        L.rec[p] = rec[i];
         L.bin[p] = (uint16_t)b;
       }
     }
@@ -1990,15 +1969,6 @@ __global__ __launch_bounds__(kBlock) void dq_freq_pieces_kernel(const unsigned l
     pieces[b] = b < n ? (uint32_t)((counts[b] + kFreqAggPiece - 1) / kFreqAggPiece) : 0u;
 }
 
-// Stage + level-1 partition fused: the rows of one batch become records written straight into
-// their level-1 regions (top b1 bits of the table hash), so the staging is not written and read
-// back in row order.  Tiles of kPartTile rows, grid-stride.  The sketch, the staged count and
-// the long-key flag are kept as by dq_freq_stage_kernel.  Single-string keys (the common case)
-// load their offsets, then their bytes, for all of a thread's rows at once.
-// PACK (single string key only): the regions hold packed digit records (uint64_t, dq_keypack.h);
-// a key that is not a digit string goes to the overflow list as a 16-B record (counted there and
-// in `staged`), and a batch with more of them than the list holds raises `flag` (the host then
-// rolls it back and stages the table's keys as 16-B records from then on).
 // A pointer every lane holds alike, in scalar registers (a buffer descriptor built from a value
 // the compiler cannot prove uniform is re-made per lane in a waterfall loop).
 template <typename T>
@@ -2038,25 +2008,28 @@ __device__ __forceinline__ uint32_t tile_valid_word(const uint8_t* validity, int
   return vword;
 }
 
-// The (begin, end) offsets of tile `tl`'s kStagePer rows of one utf8 column (row j of this thread
-// = tl * kStageTile + j * kStageThreads + threadIdx.x): one 8-byte load of each row's offset pair
-// through a descriptor of the tile's offsets (rows past the batch read 0).  The validity bits
-// come as ONE dword per lane: row j of lane l of wave w is bit l & 31 of tile dword
-// 16 j + 2 w + (l >> 5), which lane 2 j + (l >> 5) of the wave loads (stage_valid_mask).
-__device__ __forceinline__ void stage_offsets(const DevColumn& c0, int64_t n_rows, int64_t tl,
-                                              uint32_t (&pob)[kStagePer], uint32_t (&poe)[kStagePer],
-                                              uint32_t& vword) {
-  const int64_t r0 = tl * (int64_t)kStageTile;
+// The extent of tile `tl` of TILE rows: its first row (the return value) and its rows m.
+template <uint32_t TILE>
+__device__ __forceinline__ int64_t tile_extent(int64_t n_rows, int64_t tl, uint32_t& m) {
+  const int64_t r0 = tl * (int64_t)TILE;
   const int64_t left = n_rows - r0;
-  const uint32_t m = (uint32_t)(left < (int64_t)kStageTile ? left : (int64_t)kStageTile);
-  const uint32_t t = threadIdx.x;
-  // (the validity dword first: its address arithmetic waits on nothing then)
-  vword = tile_valid_word<kStageThreads, kStagePer>(uniform_ptr(c0.validity), r0, m);
-  const __amdgpu_buffer_rsrc_t rs_off = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<int32_t*>(uniform_ptr(c0.offsets) + r0), 0, (int)(4u * (m + 1u)), 0x00020000);
+  m = (uint32_t)(left < (int64_t)TILE ? left : (int64_t)TILE);
+  return r0;
+}
+
+// The (begin, end) offsets of a tile's PER rows per thread of one utf8 column (the tile's m rows
+// start at row r0; row j of this thread = r0 + j * kStageThreads + threadIdx.x): one 8-byte load
+// of each row's offset pair through a descriptor of the tile's offsets (rows past the batch
+// read 0).
+template <int PER>
+__device__ __forceinline__ void stage_offsets(const int32_t* offsets, int64_t r0, uint32_t m, uint32_t (&pob)[PER],
+                                              uint32_t (&poe)[PER]) {
+  const __amdgpu_buffer_rsrc_t rs_off =
+      __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t*>(offsets + r0), 0, (int)(4u * (m + 1u)), 0x00020000);
 #pragma unroll
-  for (int j = 0; j < kStagePer; ++j) {
-    const auto v = __builtin_amdgcn_raw_buffer_load_b64(rs_off, (int)(4u * ((uint32_t)j * kStageThreads + t)), 0, 0);
+  for (int j = 0; j < PER; ++j) {
+    const auto v =
+        __builtin_amdgcn_raw_buffer_load_b64(rs_off, (int)(4u * ((uint32_t)j * kStageThreads + threadIdx.x)), 0, 0);
     pob[j] = v[0];
     poe[j] = v[1];
   }
@@ -2102,6 +2075,23 @@ __device__ __forceinline__ void stage_sketch(uint32_t* regs, uint64_t h) {
   __hip_atomic_fetch_min(&regs[(uint32_t)(h >> kHllIdxShift)], s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 __device__ __forceinline__ uint32_t stage_sketch_rank(uint32_t s) { return s ? (uint32_t)__builtin_clz(s) : 32u; }
+// A workgroup of NT threads: its LDS registers emptied before the first row, and folded into the
+// table's sketch after the last (the caller's barrier between each and the rows' stage_sketch).
+template <int NT>
+__device__ __forceinline__ void sketch_clear(uint32_t* regs) {
+  for (uint32_t i = threadIdx.x; i < (uint32_t)kHllM; i += NT) regs[i] = 0xFFFFFFFFu;
+}
+template <int NT>
+__device__ __forceinline__ void sketch_fold(const uint32_t* regs, uint32_t* hll) {
+  for (uint32_t i = threadIdx.x; i < (uint32_t)kHllM; i += NT)
+    if (regs[i] != 0xFFFFFFFFu) atomicMax(&hll[i], stage_sketch_rank(regs[i]));
+}
+
+// A per-thread count added to *counter with one atomic per wave.
+__device__ __forceinline__ void wave_add(unsigned long long* counter, uint32_t n) {
+  for (int d = 32; d >= 1; d >>= 1) n += __shfl_xor(n, d, 64);
+  if ((threadIdx.x & 63u) == 0u && n) atomicAdd(counter, (unsigned long long)n);
+}
 
 // stage_pack's selectors for a key of n <= 15 bytes, word i: byte j of the word is the key's
 // byte (v_perm selector 4 + j, from the first operand) if 4 i + j < n, else '0' (selector 0:
@@ -2127,7 +2117,7 @@ __device__ __forceinline__ bool stage_pack(const uint32_t (&w)[4], uint32_t n, u
   return true;
 }
 
-// The validity of row j of every lane of this wave, as a lane mask (from stage_offsets' vword).
+// The validity of row j of every lane of this wave, as a lane mask (from tile_valid_word's dword).
 __device__ __forceinline__ uint64_t stage_valid_mask(uint32_t vword, int j) {
   const uint32_t lo = __builtin_amdgcn_readlane(vword, 2 * j), hi = __builtin_amdgcn_readlane(vword, 2 * j + 1);
   return ((uint64_t)hi << 32) | lo;
@@ -2144,50 +2134,50 @@ constexpr int kStageWin = DQ_STAGE_WIN < DQ_STAGE_PER ? DQ_STAGE_WIN : DQ_STAGE_
 #ifndef DQ_STAGEP_WAVES
 #define DQ_STAGEP_WAVES 4
 #endif
-template <bool ONE_STRING, bool PACK>
-__global__ __launch_bounds__(kStageThreads) __attribute__((amdgpu_waves_per_eu(DQ_STAGEP_WAVES))) void dq_freq_stage_part_kernel(
-    FreqKeySpec ks, const DevColumn* __restrict__ cols, int64_t n_rows, int b1,
-    typename std::conditional<PACK, uint64_t, FreqRec>::type* __restrict__ out, uint64_t cap1,
-    unsigned long long* fill1, FreqRec* ovf, unsigned long long* ovf_n, uint64_t ovf_cap, unsigned int* flag,
-    uint32_t* hll, unsigned long long* long_key, unsigned long long* staged) {
-  static_assert(ONE_STRING || !PACK, "packed records are staged from one string key column");
-  using R = typename std::conditional<PACK, uint64_t, FreqRec>::type;
-  __shared__ PartLdsT<(1 << kStageBinBits), R, (PACK ? kStageSubP : kStageSub16)> L;
-  __shared__ uint32_t regs[kHllM];
-  __shared__ uint4 psel[16];  // stage_pack's byte selectors by key length
-  const uint32_t t = threadIdx.x;
-  const uint32_t nb = 1u << b1;
-  for (uint32_t i = t; i < (uint32_t)kHllM; i += kStageThreads) regs[i] = 0xFFFFFFFFu;  // (stage_sketch)
-  if (PACK && t < 16u) psel[t] = make_uint4(stage_pack_sel(t, 0), stage_pack_sel(t, 1), stage_pack_sel(t, 2), stage_pack_sel(t, 3));
-#ifdef DQ_STAGE_PROF
-  if (t == 0 && blockIdx.x < 4096u) g_stage_blk[blockIdx.x][0] = wall_clock64();
-#endif
-  lds_barrier();
-  const DevColumn& c0 = cols[ks.key_cols[0]];
-  alignas(8) uint8_t scratch[kMaxLocalKey];
-  const int64_t n_tiles = (n_rows + kStageTile - 1) / kStageTile;
-  uint32_t n_side = 0;  // PACK: this thread's keys put on the overflow list (not digit strings)
-  // ONE_STRING: the key bytes through one buffer descriptor (a utf8 column's offsets are int32, so
-  // its heap is < 2 GiB); each tile's offsets through a descriptor of that tile's offsets (bounded,
-  // so rows past the batch read 0), as (begin, end) pairs: one 8-byte load per row.
-  const uint32_t heap_end = ONE_STRING ? __builtin_amdgcn_readfirstlane((uint32_t)uniform_ptr(c0.offsets)[n_rows]) : 0u;
-  const uint8_t* vals = static_cast<const uint8_t*>(uniform_ptr(c0.values));
-  const __amdgpu_buffer_rsrc_t rs_vals =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(vals), 0, (int)heap_end, 0x00020000);
-  if (ONE_STRING && heap_end < 16u) {  // (a heap under 16 bytes: key_load16's general path, as a long key)
-    if (blockIdx.x == 0 && t == 0) atomicMax(long_key, 16ull);
-    return;
+
+// The front end of the two string stages: one utf8 key column, read a tile of kStageTile rows at
+// a time.  The key bytes come through one buffer descriptor (a utf8 column's offsets are int32,
+// so its heap is < 2 GiB); each tile's offsets through a descriptor of that tile's offsets
+// (bounded, so rows past the batch read 0), as (begin, end) pairs: one 8-byte load per row.
+// A tile's key lengths are kept as bytes, 4 to a register (lens: n | s << 4 for a key of n <= 15
+// bytes at byte s of its loaded words -- key_shift; s + n <= 16, so the two codes below are
+// never taken by a key), beside its selected rows (sel) and its key words (kw).
+constexpr uint32_t kLenNull = 254u;  // Histogram's NULL, "NullValue"
+constexpr uint32_t kLenLong = 255u;  // a key over 15 bytes: the batch is rolled back
+struct StageStrings {
+  const int32_t* offsets;   // (uniform_ptr: in scalar registers)
+  const uint8_t* validity;  // (as offsets; nullptr: no NULLs)
+  int64_t n_rows;
+  int32_t null_as_key;
+  uint32_t heap_end;
+  __amdgpu_buffer_rsrc_t rs_vals;
+  uint32_t pob[kStagePer], poe[kStagePer], vword;
+  uint32_t kw[kStagePer][4], lens[(kStagePer + 3) / 4], sel;
+
+  // False (the workgroup returns): a heap under 16 bytes -- key_load16's general path, as a long key.
+  __device__ __forceinline__ bool open(const DevColumn& c, int64_t n, int32_t nulls, unsigned long long* long_key) {
+    offsets = uniform_ptr(c.offsets);
+    n_rows = n;
+    null_as_key = nulls;
+    heap_end = __builtin_amdgcn_readfirstlane((uint32_t)offsets[n_rows]);
+    const uint8_t* vals = static_cast<const uint8_t*>(uniform_ptr(c.values));
+    rs_vals = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(vals), 0, (int)heap_end, 0x00020000);
+    if (heap_end < 16u) {
+      if (blockIdx.x == 0 && threadIdx.x == 0) atomicMax(long_key, 16ull);
+      return false;
+    }
+    validity = uniform_ptr(c.validity);
+    return true;
   }
-  const bool has_validity = uniform_ptr(c0.validity) != nullptr;
-  uint32_t pob[kStagePer], poe[kStagePer], vword = 0u;
-  // ONE_STRING: a tile's key words (kw), key lengths as bytes, 4 to a register (lens: n | s << 4
-  // for a key of n <= 15 bytes at byte s of its loaded words -- key_shift; s + n <= 16, so the
-  // codes below are never taken by a key; kLenNull = Histogram's NULL, "NullValue"; kLenLong = a
-  // key over 15 bytes: the batch is rolled back) and its selected rows (sel)
-  constexpr uint32_t kLenNull = 254u, kLenLong = 255u;
-  uint32_t kw[kStagePer][4], lens[(kStagePer + 3) / 4], sel = 0u;
-  auto tile_lens = [&](int64_t tl) {  // lens / sel of tile tl, from its offsets (pob / poe / vword)
-    const int64_t r0 = tl * (int64_t)kStageTile;
+
+  // Tile tl's offsets (and validity bits: one word per lane), then lens / sel from them.
+  __device__ __forceinline__ void tile(int64_t tl) {
+    const uint32_t t = threadIdx.x;
+    uint32_t m;
+    const int64_t r0 = tile_extent<kStageTile>(n_rows, tl, m);
+    // (the validity dword first: its address arithmetic waits on nothing then)
+    vword = tile_valid_word<kStageThreads, kStagePer>(validity, r0, m);
+    stage_offsets<kStagePer>(offsets, r0, m, pob, poe);
     sel = 0u;
 #pragma unroll
     for (int j = 0; j < (kStagePer + 3) / 4; ++j) lens[j] = 0u;
@@ -2195,111 +2185,111 @@ __global__ __launch_bounds__(kStageThreads) __attribute__((amdgpu_waves_per_eu(D
     for (int j = 0; j < kStagePer; ++j) {
       const int64_t row = r0 + j * kStageThreads + t;
       const uint32_t n = poe[j] - pob[j];
-      const bool valid = !has_validity || ((stage_valid_mask(vword, j) >> (t & 63u)) & 1u);
-      if (row < n_rows && (valid || ks.null_as_key)) sel |= 1u << j;
+      const bool valid = validity == nullptr || ((stage_valid_mask(vword, j) >> (t & 63u)) & 1u);
+      if (row < n_rows && (valid || null_as_key)) sel |= 1u << j;
       const uint32_t nb8 = (row < n_rows && !valid) ? kLenNull : (n > 15u ? kLenLong : n | (key_shift(pob[j], heap_end) << 4));
       lens[j / 4] |= nb8 << (8 * (j % 4));
     }
-  };
-  // PACK: once the overflow list has filled up (a column of keys that are not digit strings) the
-  // batch will be rolled back, so the workgroups stop: thread 0 reads `flag` while each tile's
-  // room is reserved (abort_v) and the workgroup leaves at the next tile's top.
-  __shared__ unsigned int abort_s;
-  unsigned int abort_v = 0u;
-  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    if constexpr (PACK) {
-      if (tile != (int64_t)blockIdx.x) {
-        if (t == 0) abort_s = abort_v;
-        lds_barrier();
-        if (abort_s) break;
-      }
+  }
+
+  // The tile's keys, 16 bytes each from the key's first byte (key_load16), through a window of
+  // kStageWin rows in flight: rows [0, kStageWin) now, row j + kStageWin as row j is processed
+  // by row(j), which is called for every row of the tile.  (Deeper pipelines -- the next tile's
+  // offsets or keys loaded during this tile's split -- need more registers than four waves per
+  // SIMD leave; at three waves a 6-wave workgroup runs alone on its CU.)
+  template <typename Row>
+  __device__ __forceinline__ void rows(Row&& row) {
+#pragma unroll
+    for (int j = 0; j < kStageWin; ++j) key_load16(rs_vals, heap_end, pob[j], kw[j]);
+#pragma unroll
+    for (int j = 0; j < kStagePer; ++j) {
+      if (j + kStageWin < kStagePer) key_load16(rs_vals, heap_end, pob[j + kStageWin], kw[j + kStageWin]);
+      row(j);
     }
+  }
+
+  // Row j's key length n (kLenNull, or its bytes, kw[j] then holding the key from byte 0).  False:
+  // the row stages nothing -- not selected, or a key over 15 bytes (too_long raised).
+  __device__ __forceinline__ bool key_len(int j, uint32_t& n, uint32_t& too_long) {
+    if (!((sel >> j) & 1u)) return false;
+    n = (lens[j / 4] >> (8 * (j % 4))) & 0xFFu;
+    if (n == kLenLong) {  // (a key longer than 15 bytes: the host only tests > 15)
+      too_long = 16u;
+      return false;
+    }
+    if (n != kLenNull) {
+      if (n > 15u) key_shr_bytes(kw[j], n >> 4);  // a key in the heap's last 16 bytes (rare)
+      n &= 15u;
+    }
+    return true;
+  }
+
+  // the key bytes (NULL: Histogram's "NullValue"), masked to the length
+  __device__ __forceinline__ void key_words(int j, uint32_t n, uint64_t& k0, uint64_t& k1, uint32_t& len) const {
+    if (n == kLenNull) {
+      len = 9;
+      k0 = kNullK0;
+      k1 = kNullK1;
+    } else {
+      const uint64_t lo = (uint64_t)kw[j][0] | ((uint64_t)kw[j][1] << 32);
+      const uint64_t hi = (uint64_t)kw[j][2] | ((uint64_t)kw[j][3] << 32);
+      len = n;
+      k0 = n >= 8 ? lo : (lo & ((1ull << (8u * n)) - 1ull));
+      k1 = n > 8 ? (hi & ((1ull << (8u * (n - 8u))) - 1ull)) : 0ull;
+    }
+  }
+};
+
+// Stage + level-1 partition fused, for 16-byte records: the rows of one batch become FreqRecs
+// written straight into their level-1 regions (top b1 bits of the table hash), so the staging is
+// not written and read back in row order.  Tiles of kStageTile rows, grid-stride.  The sketch, the
+// staged count and the long-key flag are kept as by dq_freq_stage_kernel.  ONE_STRING: a single
+// utf8 key column (the common case) through StageStrings; otherwise make_key row by row.
+template <bool ONE_STRING>
+__global__ __launch_bounds__(kStageThreads) __attribute__((amdgpu_waves_per_eu(DQ_STAGEP_WAVES))) void dq_freq_stage_part_kernel(
+    FreqKeySpec ks, const DevColumn* __restrict__ cols, int64_t n_rows, int b1, FreqRec* __restrict__ out, uint64_t cap1,
+    unsigned long long* fill1, FreqRec* ovf, unsigned long long* ovf_n, uint64_t ovf_cap, unsigned int* flag,
+    uint32_t* hll, unsigned long long* long_key, unsigned long long* staged) {
+  __shared__ PartLdsT<(1 << kStageBinBits), FreqRec, kStageSub16> L;
+  __shared__ uint32_t regs[kHllM];
+  const uint32_t t = threadIdx.x;
+  const uint32_t nb = 1u << b1;
+  sketch_clear<kStageThreads>(regs);
+#ifdef DQ_STAGE_PROF
+  if (t == 0 && blockIdx.x < 4096u) g_stage_blk[blockIdx.x][0] = wall_clock64();
+#endif
+  lds_barrier();
+  alignas(8) uint8_t scratch[kMaxLocalKey];
+  const int64_t n_tiles = (n_rows + kStageTile - 1) / kStageTile;
+  StageStrings S;
+  if constexpr (ONE_STRING)
+    if (!S.open(cols[ks.key_cols[0]], n_rows, ks.null_as_key, long_key)) return;
+  for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
     const int64_t row0 = tile * (int64_t)kStageTile;
     unsigned long long prof_t_ = 0;
     (void)prof_t_;
     DQ_PROF_MARK(true, 0);
-    R rec[kStagePer];
+    FreqRec rec[kStagePer];
     uint32_t bin[kStagePer];
     uint32_t too_long = 0u;
     if constexpr (ONE_STRING) {
-      // The tile's offsets (and validity bits: one word per lane), then its keys 16 bytes each
-      // from the key's first byte (key_load16) through a window of kStageWin rows in flight:
-      // rows [0, kStageWin) now, row j + kStageWin as row j is processed.  (Deeper pipelines --
-      // the next tile's offsets or keys loaded during this tile's split -- need more registers
-      // than four waves per SIMD leave; at three waves a 6-wave workgroup runs alone on its CU.)
-      stage_offsets(c0, n_rows, tile, pob, poe, vword);
-      tile_lens(tile);
-#pragma unroll
-      for (int j = 0; j < kStageWin; ++j) key_load16(rs_vals, heap_end, pob[j], kw[j]);
-#pragma unroll
-      for (int j = 0; j < kStagePer; ++j) {
-        if (j + kStageWin < kStagePer) key_load16(rs_vals, heap_end, pob[j + kStageWin], kw[j + kStageWin]);
+      S.tile(tile);
+      S.rows([&](int j) __attribute__((always_inline)) {
         bin[j] = kPartNoBin;
-        if (!((sel >> j) & 1u)) continue;
-        uint32_t n = (lens[j / 4] >> (8 * (j % 4))) & 0xFFu;
-        if (n == kLenLong) {  // (a key longer than 15 bytes: the host only tests > 15)
-          too_long = 16u;
-          continue;
-        }
-        if (n != kLenNull) {
-          if (n > 15u) key_shr_bytes(kw[j], n >> 4);  // a key in the heap's last 16 bytes (rare)
-          n &= 15u;
-        }
-        // the key bytes (NULL: Histogram's "NullValue"), masked to the length
-        auto key_words = [&](uint64_t& k0, uint64_t& k1, uint32_t& len) {
-          if (n == kLenNull) {
-            len = 9;
-            k0 = kNullK0;
-            k1 = kNullK1;
-          } else {
-            const uint64_t lo = (uint64_t)kw[j][0] | ((uint64_t)kw[j][1] << 32);
-            const uint64_t hi = (uint64_t)kw[j][2] | ((uint64_t)kw[j][3] << 32);
-            len = n;
-            k0 = n >= 8 ? lo : (lo & ((1ull << (8u * n)) - 1ull));
-            k1 = n > 8 ? (hi & ((1ull << (8u * (n - 8u))) - 1ull)) : 0ull;
-          }
-        };
-        uint64_t h;
-        if constexpr (PACK) {
-          // the digit test and packing straight from the loaded words (stage_pack); NULL packs
-          // as kPackNull; anything else is checked against the "NullValue" string, then listed
-          uint64_t p = kPackNull;
-          bool packed = n == kLenNull || stage_pack(kw[j], n, psel[n], &p);
-          uint64_t k0 = 0, k1 = 0;
-          uint32_t len = 0;
-          if (!packed) {
-            key_words(k0, k1, len);
-            packed = kp_pack_record(k0, k1, len, &p);
-          }
-          if (packed) {
-            L.rec[j * kStageThreads + t] = p;  // (row order; part_tile sorts it)
-            h = hash_record_packed(p);
-          } else {  // not a digit key: a 16-B record on the overflow list
-            h = hash_raw(k0, k1, len);
-            stage_sketch(regs, h);
-            FreqRec r;
-            r.k0 = k0;
-            r.k1 = k1 | ((unsigned long long)len << kRecLenShift);
-            const unsigned long long k = atomicAdd(ovf_n, 1ull);
-            if (k < ovf_cap) ovf[k] = r;
-            else atomicOr(flag, 1u);
-            ++n_side;
-            continue;
-          }
-        } else {
-          uint64_t k0, k1;
-          uint32_t len;
-          key_words(k0, k1, len);
-          h = hash_inline(k0, k1, len);
-          rec[j].k0 = k0;
-          rec[j].k1 = k1 | ((unsigned long long)len << kRecLenShift);
-        }
+        uint32_t n;
+        if (!S.key_len(j, n, too_long)) return;
+        uint64_t k0, k1;
+        uint32_t len;
+        S.key_words(j, n, k0, k1, len);
+        const uint64_t h = hash_inline(k0, k1, len);
+        rec[j].k0 = k0;
+        rec[j].k1 = k1 | ((unsigned long long)len << kRecLenShift);
         bin[j] = (uint32_t)(h >> (64 - b1)) & (nb - 1u);
         stage_sketch(regs, h);
         // one row at a time: interleaving the twelve rows' packing and hashing would need more
         // registers than four waves per SIMD leave (the key words of the later rows are live)
         __builtin_amdgcn_sched_barrier(0);
-      }
+      });
     } else {
 #pragma unroll
       for (int i = 0; i < kStagePer; ++i) {
@@ -2316,10 +2306,8 @@ __global__ __launch_bounds__(kStageThreads) __attribute__((amdgpu_waves_per_eu(D
           too_long = max(too_long, k.len > 15 ? k.len : 16u);
           continue;
         }
-        if constexpr (!PACK) {
-          rec[i].k0 = k.k0;
-          rec[i].k1 = k.k1 | ((unsigned long long)k.len << kRecLenShift);
-        }
+        rec[i].k0 = k.k0;
+        rec[i].k1 = k.k1 | ((unsigned long long)k.len << kRecLenShift);
         bin[i] = (uint32_t)(k.hash >> (64 - b1)) & (nb - 1u);
         stage_sketch(regs, k.hash);
       }
@@ -2330,197 +2318,94 @@ __global__ __launch_bounds__(kStageThreads) __attribute__((amdgpu_waves_per_eu(D
 #else
     constexpr bool kProf = false;
 #endif
-    // PACK: thread 0 reads `flag` as the tile's room is reserved (its wait is the atomics' wait);
-    // the workgroup leaves at the next tile's top
-    auto flag_read = [&]() {
-      if constexpr (PACK)
-        if (t == 0) abort_v = __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    };
-    part_tile<kStagePer, (1 << kStageBinBits), R, (PACK ? kStageSubP : kStageSub16), kProf, DQ_STAGE_WOUT_UNROLL,
-              PACK, kStageThreads, decltype(flag_read)>(
-        L, rec, bin, nb, 0, out, cap1, fill1, ovf, ovf_n, ovf_cap, flag, staged, nullptr, prof_t_, flag_read);
+    part_tile<kStagePer, (1 << kStageBinBits), FreqRec, kStageSub16, kProf, DQ_STAGE_WOUT_UNROLL, kStageThreads>(
+        L, rec, bin, nb, 0, out, cap1, fill1, ovf, ovf_n, ovf_cap, flag, staged, nullptr, prof_t_);
   }
-  if (PACK && n_side) atomicAdd(staged, (unsigned long long)n_side);
 #ifdef DQ_STAGE_PROF
   if (t == 0 && blockIdx.x < 4096u) g_stage_blk[blockIdx.x][1] = wall_clock64();
 #endif
   lds_barrier();
-  for (uint32_t i = t; i < (uint32_t)kHllM; i += kStageThreads)
-    if (regs[i] != 0xFFFFFFFFu) atomicMax(&hll[i], stage_sketch_rank(regs[i]));
+  sketch_fold<kStageThreads>(regs, hll);
 }
 
-// The stage's first half on its own (round 5): every row of the batch becomes its record in ROW
-// order -- out[row] -- with no split, so the kernel is a pure stream (the input read once, the
-// records written with coalesced stores) that keeps the key loads of many workgroups in flight;
-// the level-1 split runs next as dq_freq_part_kernel over the row array (level 1: records of
-// 24 per thread in 6144-record LDS rounds).  Measured on one box (125M-row batches, C4): the
-// fused stage + level-1 kernel 1.36-1.40 ms, its loads + packing + sketch alone 0.47 ms, with the
-// row-order record stores 0.58 ms.  A row that stages nothing (NULL outside a Histogram, a key
-// put on the overflow list, a key over 15 bytes) holds a hole: kPackEmpty / length kRecHole,
-// which the split drops.  Sketch, long-key flag, overflow list and `staged` (the overflow list's
-// share; the split counts the rest) are kept as the fused kernel keeps them.
-template <bool ONE_STRING, bool PACK>
-__global__ __launch_bounds__(kStageThreads) __attribute__((amdgpu_waves_per_eu(DQ_STAGEP_WAVES))) void dq_freq_stage_rows_kernel(
-    FreqKeySpec ks, const DevColumn* __restrict__ cols, int64_t n_rows,
-    typename std::conditional<PACK, uint64_t, FreqRec>::type* __restrict__ out, FreqRec* ovf,
+// The stage's first half on its own (round 5), for packed digit records (uint64_t, dq_keypack.h)
+// of one utf8 key column: every row of the batch becomes its record in ROW order -- out[row] --
+// with no split, so the kernel is a pure stream (the input read once, the records written with
+// coalesced stores) that keeps the key loads of many workgroups in flight; the level-1 split
+// runs next as dq_freq_part_kernel over the row array (level 1: records of 24 per thread in
+// 6144-record LDS rounds).  Measured on one box (125M-row batches, C4): the fused stage + level-1
+// kernel 1.36-1.40 ms, its loads + packing + sketch alone 0.47 ms, with the row-order record
+// stores 0.58 ms.  A row that stages nothing (NULL outside a Histogram, a key put on the overflow
+// list, a key over 15 bytes) holds a hole, kPackEmpty, which the split drops.  A key that is not
+// a digit string goes to the overflow list as a 16-B record (counted there and in `staged`; the
+// split counts the rest), and a batch with more of them than the list holds raises `flag` (the
+// host then rolls it back and stages the table's keys as 16-B records from then on).  Sketch and
+// long-key flag are kept as the fused kernel keeps them.
+__global__ __launch_bounds__(kStageThreads) __attribute__((amdgpu_waves_per_eu(DQ_STAGEP_WAVES))) void dq_freq_stage_packed_rows_kernel(
+    FreqKeySpec ks, const DevColumn* __restrict__ cols, int64_t n_rows, uint64_t* __restrict__ out, FreqRec* ovf,
     unsigned long long* ovf_n, uint64_t ovf_cap, unsigned int* flag, uint32_t* hll, unsigned long long* long_key,
     unsigned long long* staged) {
-  static_assert(ONE_STRING || !PACK, "packed records are staged from one string key column");
   __shared__ uint32_t regs[kHllM];
   __shared__ uint4 psel[16];  // stage_pack's byte selectors by key length
   const uint32_t t = threadIdx.x;
-  for (uint32_t i = t; i < (uint32_t)kHllM; i += kStageThreads) regs[i] = 0xFFFFFFFFu;  // (stage_sketch)
-  if (PACK && t < 16u) psel[t] = make_uint4(stage_pack_sel(t, 0), stage_pack_sel(t, 1), stage_pack_sel(t, 2), stage_pack_sel(t, 3));
+  sketch_clear<kStageThreads>(regs);
+  if (t < 16u) psel[t] = make_uint4(stage_pack_sel(t, 0), stage_pack_sel(t, 1), stage_pack_sel(t, 2), stage_pack_sel(t, 3));
   lds_barrier();
-  const DevColumn& c0 = cols[ks.key_cols[0]];
-  alignas(8) uint8_t scratch[kMaxLocalKey];
   const int64_t n_tiles = (n_rows + kStageTile - 1) / kStageTile;
-  uint32_t n_side = 0;  // PACK: this thread's keys put on the overflow list (not digit strings)
-  const uint32_t heap_end = ONE_STRING ? __builtin_amdgcn_readfirstlane((uint32_t)uniform_ptr(c0.offsets)[n_rows]) : 0u;
-  const uint8_t* vals = static_cast<const uint8_t*>(uniform_ptr(c0.values));
-  const __amdgpu_buffer_rsrc_t rs_vals =
-      __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(vals), 0, (int)heap_end, 0x00020000);
-  if (ONE_STRING && heap_end < 16u) {  // (a heap under 16 bytes: key_load16's general path, as a long key)
-    if (blockIdx.x == 0 && t == 0) atomicMax(long_key, 16ull);
-    return;
-  }
-  const bool has_validity = uniform_ptr(c0.validity) != nullptr;
-  uint32_t pob[kStagePer], poe[kStagePer], vword = 0u;
-  constexpr uint32_t kLenNull = 254u, kLenLong = 255u;
-  uint32_t kw[kStagePer][4], lens[(kStagePer + 3) / 4], sel = 0u;
-  using R = typename std::conditional<PACK, uint64_t, FreqRec>::type;
-  auto hole = [&]() -> R {
-    if constexpr (PACK) {
-      return kPackEmpty;
-    } else {
-      FreqRec r;
-      r.k0 = 0ull;
-      r.k1 = (unsigned long long)kRecHole << kRecLenShift;
-      return r;
-    }
-  };
-  // PACK: once the overflow list has filled up (a column of keys that are not digit strings) the
+  uint32_t n_side = 0;  // this thread's keys put on the overflow list (not digit strings)
+  StageStrings S;
+  if (!S.open(cols[ks.key_cols[0]], n_rows, ks.null_as_key, long_key)) return;
+  // once the overflow list has filled up (a column of keys that are not digit strings) the
   // batch will be rolled back, so a wave stops at its next tile once one of its lanes found the
   // list full (no flag read per tile: the atomic's own return says it)
   bool full = false;
   for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    if constexpr (PACK)
-      if (__ballot(full)) break;
+    if (__ballot(full)) break;
     const int64_t row0 = tile * (int64_t)kStageTile;
     uint32_t too_long = 0u;
-    if constexpr (ONE_STRING) {
-      stage_offsets(c0, n_rows, tile, pob, poe, vword);
-      sel = 0u;
-#pragma unroll
-      for (int j = 0; j < (kStagePer + 3) / 4; ++j) lens[j] = 0u;
-#pragma unroll
-      for (int j = 0; j < kStagePer; ++j) {
-        const int64_t row = row0 + j * kStageThreads + t;
-        const uint32_t n = poe[j] - pob[j];
-        const bool valid = !has_validity || ((stage_valid_mask(vword, j) >> (t & 63u)) & 1u);
-        if (row < n_rows && (valid || ks.null_as_key)) sel |= 1u << j;
-        const uint32_t nb8 = (row < n_rows && !valid) ? kLenNull : (n > 15u ? kLenLong : n | (key_shift(pob[j], heap_end) << 4));
-        lens[j / 4] |= nb8 << (8 * (j % 4));
-      }
-#pragma unroll
-      for (int j = 0; j < kStageWin; ++j) key_load16(rs_vals, heap_end, pob[j], kw[j]);
-#pragma unroll
-      for (int j = 0; j < kStagePer; ++j) {
-        if (j + kStageWin < kStagePer) key_load16(rs_vals, heap_end, pob[j + kStageWin], kw[j + kStageWin]);
-        const int64_t row = row0 + j * kStageThreads + t;
-        if (row >= n_rows) continue;
-        R r = hole();
-        if ((sel >> j) & 1u) {
-          uint32_t n = (lens[j / 4] >> (8 * (j % 4))) & 0xFFu;
-          if (n == kLenLong) {
-            too_long = 16u;
-          } else {
-            if (n != kLenNull) {
-              if (n > 15u) key_shr_bytes(kw[j], n >> 4);  // a key in the heap's last 16 bytes (rare)
-              n &= 15u;
-            }
-            auto key_words = [&](uint64_t& k0, uint64_t& k1, uint32_t& len) {
-              if (n == kLenNull) {
-                len = 9;
-                k0 = kNullK0;
-                k1 = kNullK1;
-              } else {
-                const uint64_t lo = (uint64_t)kw[j][0] | ((uint64_t)kw[j][1] << 32);
-                const uint64_t hi = (uint64_t)kw[j][2] | ((uint64_t)kw[j][3] << 32);
-                len = n;
-                k0 = n >= 8 ? lo : (lo & ((1ull << (8u * n)) - 1ull));
-                k1 = n > 8 ? (hi & ((1ull << (8u * (n - 8u))) - 1ull)) : 0ull;
-              }
-            };
-            if constexpr (PACK) {
-              uint64_t p = kPackNull;
-              bool packed = n == kLenNull || stage_pack(kw[j], n, psel[n], &p);
-              uint64_t k0 = 0, k1 = 0;
-              uint32_t len = 0;
-              if (!packed) {
-                key_words(k0, k1, len);
-                packed = kp_pack_record(k0, k1, len, &p);
-              }
-              if (packed) {
-                r = p;
-                stage_sketch(regs, hash_record_packed(p));
-              } else {  // not a digit key: a 16-B record on the overflow list, a hole in the rows
-                stage_sketch(regs, hash_raw(k0, k1, len));
-                FreqRec o;
-                o.k0 = k0;
-                o.k1 = k1 | ((unsigned long long)len << kRecLenShift);
-                const unsigned long long k = atomicAdd(ovf_n, 1ull);
-                if (k < ovf_cap) {
-                  ovf[k] = o;
-                } else {
-                  atomicOr(flag, 1u);
-                  full = true;
-                }
-                ++n_side;
-              }
-            } else {
-              uint64_t k0, k1;
-              uint32_t len;
-              key_words(k0, k1, len);
-              stage_sketch(regs, hash_inline(k0, k1, len));
-              r.k0 = k0;
-              r.k1 = k1 | ((unsigned long long)len << kRecLenShift);
-            }
-          }
+    S.tile(tile);
+    S.rows([&](int j) __attribute__((always_inline)) {
+      const int64_t row = row0 + j * kStageThreads + t;
+      if (row >= n_rows) return;
+      uint64_t r = kPackEmpty;
+      uint32_t n;
+      if (S.key_len(j, n, too_long)) {
+        // the digit test and packing straight from the loaded words (stage_pack); NULL packs
+        // as kPackNull; anything else is checked against the "NullValue" string, then listed
+        uint64_t p = kPackNull;
+        bool packed = n == kLenNull || stage_pack(S.kw[j], n, psel[n], &p);
+        uint64_t k0 = 0, k1 = 0;
+        uint32_t len = 0;
+        if (!packed) {
+          S.key_words(j, n, k0, k1, len);
+          packed = kp_pack_record(k0, k1, len, &p);
         }
-        out[row] = r;
-        __builtin_amdgcn_sched_barrier(0);
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < kStagePer; ++i) {
-        const int64_t row = row0 + i * kStageThreads + t;
-        if (row >= n_rows) continue;
-        R r = hole();
-        Key k;
-        bool tl;
-        if (make_key(ks, cols, row, k, scratch, tl)) {
-          if (k.len > 15 || k.ptr != nullptr) {
-            too_long = max(too_long, k.len > 15 ? k.len : 16u);
+        if (packed) {
+          r = p;
+          stage_sketch(regs, hash_record_packed(p));
+        } else {  // not a digit key: a 16-B record on the overflow list, a hole in the rows
+          stage_sketch(regs, hash_raw(k0, k1, len));
+          FreqRec o;
+          o.k0 = k0;
+          o.k1 = k1 | ((unsigned long long)len << kRecLenShift);
+          const unsigned long long k = atomicAdd(ovf_n, 1ull);
+          if (k < ovf_cap) {
+            ovf[k] = o;
           } else {
-            if constexpr (!PACK) {
-              r.k0 = k.k0;
-              r.k1 = k.k1 | ((unsigned long long)k.len << kRecLenShift);
-            }
-            stage_sketch(regs, k.hash);
+            atomicOr(flag, 1u);
+            full = true;
           }
-        } else if (tl) {
-          too_long = max(too_long, (uint32_t)kMaxLocalKey + 1u);
+          ++n_side;
         }
-        out[row] = r;
       }
-    }
+      out[row] = r;
+      __builtin_amdgcn_sched_barrier(0);  // (one row at a time, as the fused kernel)
+    });
     if (too_long) atomicMax(long_key, (unsigned long long)too_long);
   }
-  if (PACK && n_side) atomicAdd(staged, (unsigned long long)n_side);
+  if (n_side) atomicAdd(staged, (unsigned long long)n_side);
   lds_barrier();
-  for (uint32_t i = t; i < (uint32_t)kHllM; i += kStageThreads)
-    if (regs[i] != 0xFFFFFFFFu) atomicMax(&hll[i], stage_sketch_rank(regs[i]));
+  sketch_fold<kStageThreads>(regs, hll);
 }
 
 // Copy regions (min(fill, cap) records each) to out[prefix[r] ..]: the partitioned staging
@@ -3020,17 +2905,68 @@ constexpr int kHashPer = 16;
 constexpr int kHashG = 2;      // rows whose words are in flight together
 constexpr int kHashWords = 6;  // register path: keys of <= 48 bytes
 constexpr uint32_t kHashTile = (uint32_t)kBlock * kHashPer;
+
+// The heap offset of `row`'s key within its wave's run (8-byte padded key lengths, one wave
+// prefix per row of the lanes); `run` grows by the 64 rows' bytes.
+__device__ __forceinline__ uint32_t hashed_row_offset(const FreqKeySpec& ks, const DevColumn* cols, int64_t row,
+                                                      int64_t n_rows, uint32_t& run) {
+  const uint32_t lane = threadIdx.x & 63u;
+  uint32_t n = 0u, m8 = 0u;
+  if (row < n_rows && key_len_of(ks, cols, row, &n)) m8 = (n + 7u) & ~7u;
+  uint32_t x = m8;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint32_t y = __shfl_up(x, d, 64);
+    if (lane >= (uint32_t)d) x += y;
+  }
+  const uint32_t off = run + x - m8;
+  run += __shfl(x, 63, 64);
+  return off;
+}
+
+// The tile's ONE heap reservation, from each wave's `run` bytes: `base` = the heap offset of this
+// wave's run.  False, with the table's overflow bit raised: the heap has no room for the tile.
+// (The caller's barrier at the tile's end: wsum and tile_base are rewritten by the next tile.)
+__device__ __forceinline__ bool hashed_reserve(const FreqTable& T, uint32_t run, unsigned long long& base) {
+  static_assert(kBlock / 64 <= 4, "four waves");
+  __shared__ uint32_t wsum[4];
+  __shared__ unsigned long long tile_base;
+  const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+  if (lane == 0u) wsum[wave] = run;
+  __syncthreads();
+  uint32_t before = 0u, total = 0u;
+#pragma unroll
+  for (int w = 0; w < kBlock / 64; ++w) {
+    before += (uint32_t)w < wave ? wsum[w] : 0u;
+    total += wsum[w];
+  }
+  if (t == 0) tile_base = total ? atomicAdd(T.heap_used, (unsigned long long)total) : 0ull;
+  __syncthreads();
+  base = tile_base + before;
+  const bool room = tile_base + total <= T.heap_cap;  // (the host sized the heap: never false)
+  if (!room && t == 0) atomicOr(T.overflow, 2u);
+  return room;
+}
+
+// A hashed stage's end: its threads' key count, longest key and too-long flag, and its sketch.
+__device__ __forceinline__ void hashed_finish(unsigned long long n_keys, uint32_t longest, bool tl_any,
+                                              unsigned long long* staged, unsigned long long* max_len,
+                                              unsigned long long* too_long, const uint32_t* regs, uint32_t* hll) {
+  for (int d = 32; d >= 1; d >>= 1) n_keys += __shfl_xor(n_keys, d, 64);
+  if (staged && (threadIdx.x & 63u) == 0u && n_keys) atomicAdd(staged, n_keys);
+  if (max_len && longest) atomicMax(max_len, (unsigned long long)longest);
+  if (tl_any) atomicMax(too_long, (unsigned long long)kMaxLocalKey + 1ull);
+  sketch_fold<kBlock>(regs, hll);
+}
+
 template <bool ONE_STRING>
 __global__ __launch_bounds__(kBlock) void dq_freq_stage_hashed_kernel(FreqKeySpec ks, const DevColumn* __restrict__ cols,
                                                                       int64_t n_rows, HashRec* __restrict__ out, FreqTable T,
                                                                       uint32_t* hll, unsigned long long* too_long,
                                                                       unsigned long long* staged,
                                                                       unsigned long long* max_len) {
-  static_assert(kBlock / 64 <= 4, "four waves");
   __shared__ uint32_t regs[kHllM];
-  __shared__ uint32_t wsum[4];
-  __shared__ unsigned long long tile_base;
-  for (uint32_t i = threadIdx.x; i < (uint32_t)kHllM; i += kBlock) regs[i] = 0xFFFFFFFFu;  // (stage_sketch)
+  sketch_clear<kBlock>(regs);
   __syncthreads();
   const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
   constexpr bool one_string = ONE_STRING;  // (the host: ks.n_keys == 1 and a utf8 column)
@@ -3045,32 +2981,9 @@ __global__ __launch_bounds__(kBlock) void dq_freq_stage_hashed_kernel(FreqKeySpe
     uint32_t off[kHashPer];  // heap offset of row j within the wave's run
     uint32_t run = 0u;
 #pragma unroll
-    for (int j = 0; j < kHashPer; ++j) {
-      const int64_t row = rw + 64 * j;
-      uint32_t n = 0u, m8 = 0u;
-      if (row < n_rows && key_len_of(ks, cols, row, &n)) m8 = (n + 7u) & ~7u;
-      uint32_t x = m8;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t y = __shfl_up(x, d, 64);
-        if (lane >= (uint32_t)d) x += y;
-      }
-      off[j] = run + x - m8;
-      run += __shfl(x, 63, 64);
-    }
-    if (lane == 0u) wsum[wave] = run;
-    __syncthreads();
-    uint32_t before = 0u, total = 0u;
-#pragma unroll
-    for (int w = 0; w < kBlock / 64; ++w) {
-      before += (uint32_t)w < wave ? wsum[w] : 0u;
-      total += wsum[w];
-    }
-    if (t == 0) tile_base = total ? atomicAdd(T.heap_used, (unsigned long long)total) : 0ull;
-    __syncthreads();
-    const unsigned long long base = tile_base + before;
-    const bool room = tile_base + total <= T.heap_cap;  // (the host sized the heap: never false)
-    if (!room && t == 0) atomicOr(T.overflow, 2u);
+    for (int j = 0; j < kHashPer; ++j) off[j] = hashed_row_offset(ks, cols, rw + 64 * j, n_rows, run);
+    unsigned long long base;
+    const bool room = hashed_reserve(T, run, base);
 #pragma unroll
     for (int g = 0; g < kHashPer; g += kHashG) {
       int32_t ob[kHashG], oe[kHashG];
@@ -3147,14 +3060,9 @@ __global__ __launch_bounds__(kBlock) void dq_freq_stage_hashed_kernel(FreqKeySpe
         out[row] = r;
       }
     }
-    __syncthreads();  // (wsum and tile_base are rewritten by the next tile)
+    __syncthreads();  // (hashed_reserve's LDS words are rewritten by the next tile)
   }
-  for (int d = 32; d >= 1; d >>= 1) n_keys += __shfl_xor(n_keys, d, 64);
-  if (staged && lane == 0u && n_keys) atomicAdd(staged, n_keys);
-  if (max_len && longest) atomicMax(max_len, (unsigned long long)longest);
-  if (tl_any) atomicMax(too_long, (unsigned long long)kMaxLocalKey + 1ull);
-  for (uint32_t i = t; i < (uint32_t)kHllM; i += kBlock)
-    if (regs[i] != 0xFFFFFFFFu) atomicMax(&hll[i], stage_sketch_rank(regs[i]));
+  hashed_finish(n_keys, longest, tl_any, staged, max_len, too_long, regs, hll);
 }
 
 // The hashed stage of a multi-column key (round 6): dq_freq_stage_hashed_kernel<false>'s
@@ -3168,12 +3076,9 @@ __global__ __launch_bounds__(kBlock) void dq_freq_stage_hashed_multi_kernel(Freq
                                                                             unsigned long long* too_long,
                                                                             unsigned long long* staged,
                                                                             unsigned long long* max_len) {
-  static_assert(kBlock / 64 <= 4, "four waves");
   __shared__ uint32_t regs[kHllM];
   __shared__ uint32_t offs[kHashPer][kBlock];
-  __shared__ uint32_t wsum[4];
-  __shared__ unsigned long long tile_base;
-  for (uint32_t i = threadIdx.x; i < (uint32_t)kHllM; i += kBlock) regs[i] = 0xFFFFFFFFu;  // (stage_sketch)
+  sketch_clear<kBlock>(regs);
   __syncthreads();
   const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
   unsigned long long n_keys = 0;
@@ -3184,32 +3089,9 @@ __global__ __launch_bounds__(kBlock) void dq_freq_stage_hashed_multi_kernel(Freq
     const int64_t rw = tile * (int64_t)kHashTile + (int64_t)wave * 64 * kHashPer + lane;  // row of j = 0
     uint32_t run = 0u;
 #pragma unroll 1
-    for (int j = 0; j < kHashPer; ++j) {
-      const int64_t row = rw + 64 * j;
-      uint32_t n = 0u, m8 = 0u;
-      if (row < n_rows && key_len_of(ks, cols, row, &n)) m8 = (n + 7u) & ~7u;
-      uint32_t x = m8;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t y = __shfl_up(x, d, 64);
-        if (lane >= (uint32_t)d) x += y;
-      }
-      offs[j][t] = run + x - m8;
-      run += __shfl(x, 63, 64);
-    }
-    if (lane == 0u) wsum[wave] = run;
-    __syncthreads();
-    uint32_t before = 0u, total = 0u;
-#pragma unroll
-    for (int w = 0; w < kBlock / 64; ++w) {
-      before += (uint32_t)w < wave ? wsum[w] : 0u;
-      total += wsum[w];
-    }
-    if (t == 0) tile_base = total ? atomicAdd(T.heap_used, (unsigned long long)total) : 0ull;
-    __syncthreads();
-    const unsigned long long base = tile_base + before;
-    const bool room = tile_base + total <= T.heap_cap;  // (the host sized the heap: never false)
-    if (!room && t == 0) atomicOr(T.overflow, 2u);
+    for (int j = 0; j < kHashPer; ++j) offs[j][t] = hashed_row_offset(ks, cols, rw + 64 * j, n_rows, run);
+    unsigned long long base;
+    const bool room = hashed_reserve(T, run, base);
 #pragma unroll 1
     for (int j = 0; j < kHashPer; ++j) {
       const int64_t row = rw + 64 * j;
@@ -3239,14 +3121,9 @@ __global__ __launch_bounds__(kBlock) void dq_freq_stage_hashed_multi_kernel(Freq
       }
       out[row] = r;
     }
-    __syncthreads();  // (offs, wsum and tile_base are rewritten by the next tile)
+    __syncthreads();  // (offs and hashed_reserve's LDS words are rewritten by the next tile)
   }
-  for (int d = 32; d >= 1; d >>= 1) n_keys += __shfl_xor(n_keys, d, 64);
-  if (staged && lane == 0u && n_keys) atomicAdd(staged, n_keys);
-  if (max_len && longest) atomicMax(max_len, (unsigned long long)longest);
-  if (tl_any) atomicMax(too_long, (unsigned long long)kMaxLocalKey + 1ull);
-  for (uint32_t i = t; i < (uint32_t)kHllM; i += kBlock)
-    if (regs[i] != 0xFFFFFFFFu) atomicMax(&hll[i], stage_sketch_rank(regs[i]));
+  hashed_finish(n_keys, longest, tl_any, staged, max_len, too_long, regs, hll);
 }
 
 // The key of a hashed record, its bytes read from (and, when long, left in) T's heap.
@@ -3679,7 +3556,7 @@ __global__ __launch_bounds__(kStageThreads) __attribute__((amdgpu_waves_per_eu(D
   __shared__ uint32_t regs[kHllM];
   const uint32_t t = threadIdx.x;
   const uint32_t nb = 1u << b1;
-  for (uint32_t i = t; i < (uint32_t)kHllM; i += kStageThreads) regs[i] = 0xFFFFFFFFu;  // (stage_sketch)
+  sketch_clear<kStageThreads>(regs);
   lds_barrier();
   const DevColumn& c0 = cols[ks.key_cols[0]];
   const int32_t* offs = uniform_ptr(c0.offsets);
@@ -3690,19 +3567,11 @@ __global__ __launch_bounds__(kStageThreads) __attribute__((amdgpu_waves_per_eu(D
   const int64_t n_tiles = (n_rows + kUuidTile - 1) / kUuidTile;
   uint32_t n_bad = 0u;
   for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    const int64_t r0 = tile * (int64_t)kUuidTile;
-    const int64_t left = n_rows - r0;
-    const uint32_t m = (uint32_t)(left < (int64_t)kUuidTile ? left : (int64_t)kUuidTile);
+    uint32_t m;
+    const int64_t r0 = tile_extent<kUuidTile>(n_rows, tile, m);
     const uint32_t vword = tile_valid_word<kStageThreads, kUuidPer>(validity, r0, m);
-    const __amdgpu_buffer_rsrc_t rs_off =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t*>(offs + r0), 0, (int)(4u * (m + 1u)), 0x00020000);
-    uint32_t pob[kUuidPer], len[kUuidPer];
-#pragma unroll
-    for (int j = 0; j < kUuidPer; ++j) {
-      const auto v = __builtin_amdgcn_raw_buffer_load_b64(rs_off, (int)(4u * ((uint32_t)j * kStageThreads + t)), 0, 0);
-      pob[j] = v[0];
-      len[j] = v[1] - v[0];
-    }
+    uint32_t pob[kUuidPer], poe[kUuidPer];
+    stage_offsets<kUuidPer>(offs, r0, m, pob, poe);
     UuidRec rec[kUuidPer];
     uint32_t bin[kUuidPer];
     uint32_t kw[kUuidWin][9];
@@ -3720,7 +3589,7 @@ __global__ __launch_bounds__(kStageThreads) __attribute__((amdgpu_waves_per_eu(D
       const bool valid = validity == nullptr || ((stage_valid_mask(vword, j) >> (t & 63u)) & 1u);
       if (i >= m || !valid) continue;
       uint64_t lo, hi;
-      if (len[j] != kUuidLen || !uuid_pack(w, &lo, &hi)) {
+      if (poe[j] - pob[j] != kUuidLen || !uuid_pack(w, &lo, &hi)) {
         ++n_bad;
         continue;
       }
@@ -3730,14 +3599,12 @@ __global__ __launch_bounds__(kStageThreads) __attribute__((amdgpu_waves_per_eu(D
       bin[j] = (uint32_t)(h >> (64 - b1)) & (nb - 1u);
       stage_sketch(regs, h);
     }
-    part_tile<kUuidPer, (1 << kStageBinBits), UuidRec, kPartSub, false, DQ_STAGE_WOUT_UNROLL, false, kStageThreads>(
+    part_tile<kUuidPer, (1 << kStageBinBits), UuidRec, kPartSub, false, DQ_STAGE_WOUT_UNROLL, kStageThreads>(
         L, rec, bin, nb, 0, out, cap1, fill1, ovf, ovf_n, ovf_cap, flag, staged);
   }
-  for (int d = 32; d >= 1; d >>= 1) n_bad += __shfl_xor(n_bad, d, 64);
-  if ((t & 63u) == 0u && n_bad) atomicAdd(bad_keys, (unsigned long long)n_bad);
+  wave_add(bad_keys, n_bad);
   lds_barrier();
-  for (uint32_t i = t; i < (uint32_t)kHllM; i += kStageThreads)
-    if (regs[i] != 0xFFFFFFFFu) atomicMax(&hll[i], stage_sketch_rank(regs[i]));
+  sketch_fold<kStageThreads>(regs, hll);
 }
 
 // Stage + level-1 split of 16-byte keys as Raw16Rec (round 6): STRING -- one utf8 column whose
@@ -3754,7 +3621,7 @@ __global__ __launch_bounds__(kStageThreads) __attribute__((amdgpu_waves_per_eu(D
   __shared__ uint32_t regs[kHllM];
   const uint32_t t = threadIdx.x;
   const uint32_t nb = 1u << b1;
-  for (uint32_t i = t; i < (uint32_t)kHllM; i += kStageThreads) regs[i] = 0xFFFFFFFFu;  // (stage_sketch)
+  sketch_clear<kStageThreads>(regs);
   lds_barrier();
   const DevColumn& c0 = cols[ks.key_cols[0]];
   const DevColumn& c1 = cols[ks.key_cols[STRING ? 0 : 1]];
@@ -3769,29 +3636,21 @@ __global__ __launch_bounds__(kStageThreads) __attribute__((amdgpu_waves_per_eu(D
   const int64_t n_tiles = (n_rows + kUuidTile - 1) / kUuidTile;
   uint32_t n_bad = 0u;
   for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-    const int64_t r0 = tile * (int64_t)kUuidTile;
-    const int64_t left = n_rows - r0;
-    const uint32_t m = (uint32_t)(left < (int64_t)kUuidTile ? left : (int64_t)kUuidTile);
+    uint32_t m;
+    const int64_t r0 = tile_extent<kUuidTile>(n_rows, tile, m);
     const uint32_t vword0 = tile_valid_word<kStageThreads, kUuidPer>(validity0, r0, m);
     const uint32_t vword1 = STRING ? 0u : tile_valid_word<kStageThreads, kUuidPer>(validity1, r0, m);
     Raw16Rec rec[kUuidPer];
     uint32_t bin[kUuidPer];
     if constexpr (STRING) {
-      const __amdgpu_buffer_rsrc_t rs_off =
-          __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t*>(offs + r0), 0, (int)(4u * (m + 1u)), 0x00020000);
-      uint32_t pob[kUuidPer], len[kUuidPer];
-#pragma unroll
-      for (int j = 0; j < kUuidPer; ++j) {
-        const auto v = __builtin_amdgcn_raw_buffer_load_b64(rs_off, (int)(4u * ((uint32_t)j * kStageThreads + t)), 0, 0);
-        pob[j] = v[0];
-        len[j] = v[1] - v[0];
-      }
+      uint32_t pob[kUuidPer], poe[kUuidPer];
+      stage_offsets<kUuidPer>(offs, r0, m, pob, poe);
 #pragma unroll
       for (int j = 0; j < kUuidPer; ++j) {
         const auto w = __builtin_amdgcn_raw_buffer_load_b128(rs_vals, (int)pob[j], 0, 0);
         rec[j].lo = (unsigned long long)w[0] | ((unsigned long long)w[1] << 32);
         rec[j].hi = (unsigned long long)w[2] | ((unsigned long long)w[3] << 32);
-        bin[j] = len[j];  // (the length, until the row is checked below)
+        bin[j] = poe[j] - pob[j];  // (the length, until the row is checked below)
       }
     } else {
 #pragma unroll
@@ -3821,14 +3680,12 @@ __global__ __launch_bounds__(kStageThreads) __attribute__((amdgpu_waves_per_eu(D
       bin[j] = (uint32_t)(h >> (64 - b1)) & (nb - 1u);
       stage_sketch(regs, h);
     }
-    part_tile<kUuidPer, (1 << kStageBinBits), Raw16Rec, kPartSub, false, DQ_STAGE_WOUT_UNROLL, false, kStageThreads>(
+    part_tile<kUuidPer, (1 << kStageBinBits), Raw16Rec, kPartSub, false, DQ_STAGE_WOUT_UNROLL, kStageThreads>(
         L, rec, bin, nb, 0, out, cap1, fill1, ovf, ovf_n, ovf_cap, flag, staged);
   }
-  for (int d = 32; d >= 1; d >>= 1) n_bad += __shfl_xor(n_bad, d, 64);
-  if ((t & 63u) == 0u && n_bad) atomicAdd(bad_keys, (unsigned long long)n_bad);
+  wave_add(bad_keys, n_bad);
   lds_barrier();
-  for (uint32_t i = t; i < (uint32_t)kHllM; i += kStageThreads)
-    if (regs[i] != 0xFFFFFFFFu) atomicMax(&hll[i], stage_sketch_rank(regs[i]));
+  sketch_fold<kStageThreads>(regs, hll);
 }
 
 // The owner aggregation of slice regions of UUID records into a FRESH table.  LDS image: the
@@ -4417,69 +4274,50 @@ hipError_t launch_freq_stage_save(const unsigned long long* d_fill, unsigned lon
   return hipGetLastError();
 }
 
-hipError_t launch_freq_stage_part(const FreqKeySpec& ks, bool one_string, bool packed, const DevColumn* d_cols,
-                                  int64_t n_rows, int b1, void* d_out,
-                                  uint64_t cap1, unsigned long long* d_fill1, FreqRec* d_ovf, unsigned long long* d_ovf_n,
-                                  uint64_t ovf_cap, unsigned int* d_flag, uint32_t* d_hll, unsigned long long* d_long_key,
-                                  unsigned long long* d_staged, hipStream_t stream, void* d_rows) {
-  if (n_rows <= 0) return hipSuccess;
-  if (b1 < 1 || b1 > kStageBinBits || (packed && !one_string)) return hipErrorInvalidValue;
-  const int64_t tiles = (n_rows + kStageTile - 1) / kStageTile;
+// The grid of a grid-stride kernel over `tiles` tiles: one resident round of its workgroups.
+template <typename K>
+static unsigned resident_grid(K kernel, int threads, int64_t tiles) {
   int dev = 0, cus = 256, per_cu = 2;
   if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (d_rows) {  // row-order staging, then the level-1 split over the rows (dq_freq_stage_rows_kernel)
-    if (packed)
-      (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, dq_freq_stage_rows_kernel<true, true>, kStageThreads, 0);
-    else if (one_string)
-      (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, dq_freq_stage_rows_kernel<true, false>, kStageThreads, 0);
-    else
-      (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, dq_freq_stage_rows_kernel<false, false>, kStageThreads, 0);
-    const int64_t resident = (int64_t)cus * (per_cu > 0 ? per_cu : 1);
-    const int64_t blocks = tiles < resident ? tiles : resident;
-    if (packed)
-      hipLaunchKernelGGL((dq_freq_stage_rows_kernel<true, true>), dim3((unsigned)blocks), dim3(kStageThreads), 0, stream, ks,
-                         d_cols, n_rows, static_cast<uint64_t*>(d_rows), d_ovf, d_ovf_n, ovf_cap, d_flag, d_hll,
-                         d_long_key, d_staged);
-    else if (one_string)
-      hipLaunchKernelGGL((dq_freq_stage_rows_kernel<true, false>), dim3((unsigned)blocks), dim3(kStageThreads), 0, stream, ks,
-                         d_cols, n_rows, static_cast<FreqRec*>(d_rows), d_ovf, d_ovf_n, ovf_cap, d_flag, d_hll,
-                         d_long_key, d_staged);
-    else
-      hipLaunchKernelGGL((dq_freq_stage_rows_kernel<false, false>), dim3((unsigned)blocks), dim3(kStageThreads), 0, stream, ks,
-                         d_cols, n_rows, static_cast<FreqRec*>(d_rows), d_ovf, d_ovf_n, ovf_cap, d_flag, d_hll,
-                         d_long_key, d_staged);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    return launch_freq_part(d_rows, (uint64_t)n_rows, nullptr, 0, 0, b1, b1, d_out, cap1, d_fill1, d_ovf, d_ovf_n, ovf_cap,
-                            d_flag, packed, stream, d_staged);
-  }
-  // one resident round of workgroups (grid-stride over the tiles)
-  if (packed)
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, dq_freq_stage_part_kernel<true, true>, kStageThreads, 0);
-  else if (one_string)
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, dq_freq_stage_part_kernel<true, false>, kStageThreads, 0);
-  else
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, dq_freq_stage_part_kernel<false, false>, kStageThreads, 0);
+  (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, 0);
   const int64_t resident = (int64_t)cus * (per_cu > 0 ? per_cu : 1);
-  const int64_t blocks = tiles < resident ? tiles : resident;
+  return (unsigned)(tiles < resident ? tiles : resident);
+}
+
+hipError_t launch_freq_stage_packed_rows(const FreqKeySpec& ks, const DevColumn* d_cols, int64_t n_rows, int b1,
+                                         uint64_t* d_rows, uint64_t* d_out, uint64_t cap1, unsigned long long* d_fill1,
+                                         FreqRec* d_ovf, unsigned long long* d_ovf_n, uint64_t ovf_cap, unsigned int* d_flag,
+                                         uint32_t* d_hll, unsigned long long* d_long_key, unsigned long long* d_staged,
+                                         hipStream_t stream) {
+  if (n_rows <= 0) return hipSuccess;
+  if (b1 < 1 || b1 > kStageBinBits) return hipErrorInvalidValue;
+  const int64_t tiles = (n_rows + kStageTile - 1) / kStageTile;
+  hipLaunchKernelGGL(dq_freq_stage_packed_rows_kernel,
+                     dim3(resident_grid(dq_freq_stage_packed_rows_kernel, kStageThreads, tiles)), dim3(kStageThreads), 0,
+                     stream, ks, d_cols, n_rows, d_rows, d_ovf, d_ovf_n, ovf_cap, d_flag, d_hll, d_long_key, d_staged);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  return launch_freq_part(d_rows, (uint64_t)n_rows, nullptr, 0, 0, b1, b1, d_out, cap1, d_fill1, d_ovf, d_ovf_n, ovf_cap,
+                          d_flag, kRecPacked, stream, d_staged);
+}
+
+hipError_t launch_freq_stage_part(const FreqKeySpec& ks, bool one_string, const DevColumn* d_cols, int64_t n_rows, int b1,
+                                  FreqRec* d_out, uint64_t cap1, unsigned long long* d_fill1, FreqRec* d_ovf,
+                                  unsigned long long* d_ovf_n, uint64_t ovf_cap, unsigned int* d_flag, uint32_t* d_hll,
+                                  unsigned long long* d_long_key, unsigned long long* d_staged, hipStream_t stream) {
+  if (n_rows <= 0) return hipSuccess;
+  if (b1 < 1 || b1 > kStageBinBits) return hipErrorInvalidValue;
+  const int64_t tiles = (n_rows + kStageTile - 1) / kStageTile;
+  const auto kernel = one_string ? dq_freq_stage_part_kernel<true> : dq_freq_stage_part_kernel<false>;
+  const unsigned blocks = resident_grid(kernel, kStageThreads, tiles);
 #ifdef DQ_STAGE_PROF
   {
     unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     (void)hipMemcpyToSymbolAsync(HIP_SYMBOL(g_stage_prof), z, sizeof(z), 0, hipMemcpyHostToDevice, stream);
   }
 #endif
-  if (packed)
-    hipLaunchKernelGGL((dq_freq_stage_part_kernel<true, true>), dim3((unsigned)blocks), dim3(kStageThreads), 0, stream, ks,
-                       d_cols, n_rows, b1, static_cast<uint64_t*>(d_out), cap1, d_fill1, d_ovf, d_ovf_n, ovf_cap, d_flag,
-                       d_hll, d_long_key, d_staged);
-  else if (one_string)
-    hipLaunchKernelGGL((dq_freq_stage_part_kernel<true, false>), dim3((unsigned)blocks), dim3(kStageThreads), 0, stream, ks,
-                       d_cols, n_rows, b1, static_cast<FreqRec*>(d_out), cap1, d_fill1, d_ovf, d_ovf_n, ovf_cap, d_flag,
-                       d_hll, d_long_key, d_staged);
-  else
-    hipLaunchKernelGGL((dq_freq_stage_part_kernel<false, false>), dim3((unsigned)blocks), dim3(kStageThreads), 0, stream, ks,
-                       d_cols, n_rows, b1, static_cast<FreqRec*>(d_out), cap1, d_fill1, d_ovf, d_ovf_n, ovf_cap, d_flag,
-                       d_hll, d_long_key, d_staged);
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(kStageThreads), 0, stream, ks, d_cols, n_rows, b1, d_out, cap1, d_fill1,
+                     d_ovf, d_ovf_n, ovf_cap, d_flag, d_hll, d_long_key, d_staged);
 #ifdef DQ_STAGE_PROF
   {
     unsigned long long z[8];
@@ -4575,12 +4413,8 @@ hipError_t launch_freq_stage_uuid(const FreqKeySpec& ks, const DevColumn* d_cols
   if (n_rows <= 0) return hipSuccess;
   if (b1 < 1 || b1 > kStageBinBits) return hipErrorInvalidValue;
   const int64_t tiles = (n_rows + kUuidTile - 1) / kUuidTile;
-  int dev = 0, cus = 256, per_cu = 2;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, dq_freq_stage_uuid_kernel, kStageThreads, 0);
-  const int64_t resident = (int64_t)cus * (per_cu > 0 ? per_cu : 1);
-  const int64_t blocks = tiles < resident ? tiles : resident;  // (one resident round, grid-stride over the tiles)
-  hipLaunchKernelGGL(dq_freq_stage_uuid_kernel, dim3((unsigned)blocks), dim3(kStageThreads), 0, stream, ks, d_cols, n_rows,
+  hipLaunchKernelGGL(dq_freq_stage_uuid_kernel, dim3(resident_grid(dq_freq_stage_uuid_kernel, kStageThreads, tiles)),
+                     dim3(kStageThreads), 0, stream, ks, d_cols, n_rows,
                      b1, static_cast<UuidRec*>(d_out), cap1, d_fill1, d_ovf, d_ovf_n, ovf_cap, d_flag, d_hll, d_bad,
                      d_staged);
   return hipGetLastError();
@@ -4647,22 +4481,10 @@ hipError_t launch_freq_stage_raw16(const FreqKeySpec& ks, bool one_string, const
   if (n_rows <= 0) return hipSuccess;
   if (b1 < 1 || b1 > kStageBinBits || (!one_string && ks.n_keys != 2)) return hipErrorInvalidValue;
   const int64_t tiles = (n_rows + kUuidTile - 1) / kUuidTile;
-  int dev = 0, cus = 256, per_cu = 2;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  if (one_string)
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, dq_freq_stage_raw16_kernel<true>, kStageThreads, 0);
-  else
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, dq_freq_stage_raw16_kernel<false>, kStageThreads, 0);
-  const int64_t resident = (int64_t)cus * (per_cu > 0 ? per_cu : 1);
-  const int64_t blocks = tiles < resident ? tiles : resident;
-  if (one_string)
-    hipLaunchKernelGGL(dq_freq_stage_raw16_kernel<true>, dim3((unsigned)blocks), dim3(kStageThreads), 0, stream, ks, d_cols,
-                       n_rows, b1, static_cast<Raw16Rec*>(d_out), cap1, d_fill1, d_ovf, d_ovf_n, ovf_cap, d_flag, d_hll,
-                       d_bad, d_staged);
-  else
-    hipLaunchKernelGGL(dq_freq_stage_raw16_kernel<false>, dim3((unsigned)blocks), dim3(kStageThreads), 0, stream, ks, d_cols,
-                       n_rows, b1, static_cast<Raw16Rec*>(d_out), cap1, d_fill1, d_ovf, d_ovf_n, ovf_cap, d_flag, d_hll,
-                       d_bad, d_staged);
+  const auto kernel = one_string ? dq_freq_stage_raw16_kernel<true> : dq_freq_stage_raw16_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3(resident_grid(kernel, kStageThreads, tiles)), dim3(kStageThreads), 0, stream, ks, d_cols,
+                     n_rows, b1, static_cast<Raw16Rec*>(d_out), cap1, d_fill1, d_ovf, d_ovf_n, ovf_cap, d_flag, d_hll,
+                     d_bad, d_staged);
   return hipGetLastError();
 }
 

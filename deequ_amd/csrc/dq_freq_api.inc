@@ -74,7 +74,6 @@ struct dq_freq : Stager {
   // A single utf8 key column stages digit keys as packed 8-byte records (dq_keypack.h) in the
   // regions; a batch whose other keys overflow the overflow list turns this off for the table.
   bool pack_default = true;                  // DQ_FREQ_PACK=0 disables (tests, A/B)
-  bool stage_rows = true;                    // row-order staging + split (DQ_FREQ_STAGE=fused: one fused kernel; A/B)
   DevBuf d_rows;                             // the row-order records of the batch being staged
   bool pack_keys = true;
   bool pack_probed = false;                  // the first packed staging sampled its keys (pack probe)
@@ -463,7 +462,50 @@ struct dq_freq : Stager {
     return DQ_OK;
   }
 
-  // Stage a batch into the regions (dq_freq_stage_part_kernel).  staged_ok = false: the batch
+  // Begin staging a batch of n_rows rows into the regions.  compatible: the regions staged so
+  // far hold the record format this batch stages; a contiguous staging, or regions of another
+  // format, are aggregated first.  The regions are (re)allocated when the batch does not fit.
+  // Then the fills, the sizing sketch and the overflow count are saved on the device (one small
+  // kernel: no host round trip before the launch; a rolled-back batch's hashes must not inflate
+  // the table's size) and the batch's longest-key counter is cleared.
+  dq_status begin_region_stage(int64_t n_rows, bool compatible) {
+    if (staged > 0 && !(region_staged && compatible)) DQ_TRY(materialize());
+    if (region_rows == 0 || staged + (uint64_t)n_rows > region_rows) {
+      if (staged > 0) DQ_TRY(materialize());
+      DQ_TRY(alloc_regions(std::max<uint64_t>((uint64_t)n_rows, reserve_rows)));
+    }
+    const uint64_t r1 = 1ull << kRegionBits;
+    unsigned long long* fill1 = static_cast<unsigned long long*>(d_pfill.ptr);
+    DQ_TRY(d_sketch_save.ensure(kHllM * sizeof(uint32_t) + sizeof(unsigned long long)));
+    uint8_t* sk_save = static_cast<uint8_t*>(d_sketch_save.ptr);
+    DQ_HIP(launch_freq_stage_save(fill1, fill1 + r1, (uint32_t)r1, static_cast<const uint32_t*>(d_sketch.ptr),
+                                  reinterpret_cast<uint32_t*>(sk_save), ctr() + FC_PART_OVF,
+                                  reinterpret_cast<unsigned long long*>(sk_save + kHllM * sizeof(uint32_t)),
+                                  ctr() + FC_MAXLEN, stream));
+    return DQ_OK;
+  }
+
+  // Roll a batch back: the fills, the sketch and the overflow count as begin_region_stage saved
+  // them, the overflow flag cleared, the staged count as it was, and the heap cursor back at
+  // *heap_used (the hashed stage; nullptr: the heap was not written).
+  dq_status rollback_region_stage(const unsigned long long* heap_used) {
+    const uint64_t r1 = 1ull << kRegionBits;
+    unsigned long long* fill1 = static_cast<unsigned long long*>(d_pfill.ptr);
+    const uint8_t* sk_save = static_cast<const uint8_t*>(d_sketch_save.ptr);
+    DQ_HIP(hipMemcpyAsync(fill1, fill1 + r1, r1 * 8, hipMemcpyDeviceToDevice, stream));
+    DQ_HIP(hipMemcpyAsync(d_sketch.ptr, sk_save, kHllM * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+    DQ_HIP(hipMemcpyAsync(ctr() + FC_PART_OVF, sk_save + kHllM * sizeof(uint32_t), sizeof(unsigned long long),
+                          hipMemcpyDeviceToDevice, stream));
+    DQ_HIP(hipMemsetAsync(ctr() + FC_PART_FLAG, 0, sizeof(unsigned long long), stream));
+    DQ_HIP(hipMemcpyAsync(ctr() + FC_STAGED, &staged, sizeof(unsigned long long), hipMemcpyHostToDevice, stream));
+    if (heap_used)
+      DQ_HIP(hipMemcpyAsync(ctr() + FC_HEAP_USED, heap_used, sizeof(unsigned long long), hipMemcpyHostToDevice, stream));
+    DQ_HIP(hipStreamSynchronize(stream));
+    return DQ_OK;
+  }
+
+  // Stage a batch into the regions (dq_freq_stage_packed_rows_kernel for packed records,
+  // dq_freq_stage_part_kernel for 16-byte ones).  staged_ok = false: the batch
   // holds a key this path cannot stage (longer than 15 bytes) or overflowed the overflow list;
   // it has been rolled back and the caller groups it on the general path.
   dq_status stage_regions(int64_t n_rows, bool& staged_ok) {
@@ -517,36 +559,27 @@ struct dq_freq : Stager {
       }
     }
     const bool packed = pack_keys && one_string;
-    // a contiguous staging, or regions of the other record format, are aggregated first
-    if (staged > 0 && (!region_staged || region_packed != packed || region_hashed)) DQ_TRY(materialize());
-    if (region_rows == 0 || staged + (uint64_t)n_rows > region_rows) {
-      if (staged > 0) DQ_TRY(materialize());
-      DQ_TRY(alloc_regions(std::max<uint64_t>((uint64_t)n_rows, reserve_rows)));
-    }
-    const uint64_t r1 = 1ull << kRegionBits;
+    DQ_TRY(begin_region_stage(n_rows, region_packed == packed && !region_hashed));
     unsigned long long* fill1 = static_cast<unsigned long long*>(d_pfill.ptr);
-    unsigned long long* save = fill1 + r1;
-    // the fills, the sizing sketch and the overflow count saved on the device (one small kernel:
-    // no host round trip before the launch); a rolled-back batch's hashes must not inflate the
-    // table's size
-    DQ_TRY(d_sketch_save.ensure(kHllM * sizeof(uint32_t) + sizeof(unsigned long long)));
-    uint8_t* sk_save = static_cast<uint8_t*>(d_sketch_save.ptr);
-    DQ_HIP(launch_freq_stage_save(fill1, save, (uint32_t)r1, static_cast<const uint32_t*>(d_sketch.ptr),
-                                  reinterpret_cast<uint32_t*>(sk_save), ctr() + FC_PART_OVF,
-                                  reinterpret_cast<unsigned long long*>(sk_save + kHllM * sizeof(uint32_t)),
-                                  ctr() + FC_MAXLEN, stream));
     region_packed = packed;  // (nothing staged, or staged in this format)
     region_hashed = false;
-    // row-order staging + the level-1 split (dq_freq_stage_rows_kernel) for packed 8-B records;
-    // 16-B records keep the fused kernel: split, they move twice the extra bytes (alnum C4,
+    // row-order staging + the level-1 split (dq_freq_stage_packed_rows_kernel) for packed 8-B
+    // records; 16-B records take the fused kernel: split, they move twice the extra bytes (alnum C4,
     // alternated on one box: 46.7 ms split against 40.3 fused, profiles/r05_c4_alnum_stage_ab.txt)
-    const bool rows = stage_rows && packed;
-    if (rows) DQ_TRY(d_rows.ensure((size_t)n_rows * sizeof(uint64_t)));
-    DQ_HIP(launch_freq_stage_part(ks, one_string, packed, static_cast<const DevColumn*>(d_cols.ptr), n_rows, kRegionBits,
-                                  d_part1.ptr, cap1, fill1, static_cast<FreqRec*>(d_povf.ptr),
-                                  ctr() + FC_PART_OVF, ovf_cap, reinterpret_cast<unsigned int*>(ctr() + FC_PART_FLAG),
-                                  static_cast<uint32_t*>(d_sketch.ptr), ctr() + FC_MAXLEN, ctr() + FC_STAGED, stream,
-                                  rows ? d_rows.ptr : nullptr));
+    const DevColumn* dcols = static_cast<const DevColumn*>(d_cols.ptr);
+    FreqRec* ovf = static_cast<FreqRec*>(d_povf.ptr);
+    unsigned int* flag = reinterpret_cast<unsigned int*>(ctr() + FC_PART_FLAG);
+    uint32_t* sketch = static_cast<uint32_t*>(d_sketch.ptr);
+    if (packed) {
+      DQ_TRY(d_rows.ensure((size_t)n_rows * sizeof(uint64_t)));
+      DQ_HIP(launch_freq_stage_packed_rows(ks, dcols, n_rows, kRegionBits, static_cast<uint64_t*>(d_rows.ptr),
+                                           static_cast<uint64_t*>(d_part1.ptr), cap1, fill1, ovf, ctr() + FC_PART_OVF,
+                                           ovf_cap, flag, sketch, ctr() + FC_MAXLEN, ctr() + FC_STAGED, stream));
+    } else {
+      DQ_HIP(launch_freq_stage_part(ks, one_string, dcols, n_rows, kRegionBits, static_cast<FreqRec*>(d_part1.ptr), cap1,
+                                    fill1, ovf, ctr() + FC_PART_OVF, ovf_cap, flag, sketch, ctr() + FC_MAXLEN,
+                                    ctr() + FC_STAGED, stream));
+    }
     unsigned long long h[FC_COUNT];
     DQ_TRY(read_counters(h));
     if (h[FC_MAXLEN] <= 15 && h[FC_PART_FLAG] == 0) {
@@ -555,14 +588,7 @@ struct dq_freq : Stager {
       staged_ok = true;
       return DQ_OK;
     }
-    // roll the batch back: the fills, the sketch, the overflow count and the staged count as they were
-    DQ_HIP(hipMemcpyAsync(fill1, save, r1 * 8, hipMemcpyDeviceToDevice, stream));
-    DQ_HIP(hipMemcpyAsync(d_sketch.ptr, sk_save, kHllM * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
-    DQ_HIP(hipMemcpyAsync(ctr() + FC_PART_OVF, sk_save + kHllM * sizeof(uint32_t), sizeof(unsigned long long),
-                          hipMemcpyDeviceToDevice, stream));
-    DQ_HIP(hipMemsetAsync(ctr() + FC_PART_FLAG, 0, sizeof(unsigned long long), stream));
-    DQ_HIP(hipMemcpyAsync(ctr() + FC_STAGED, &staged, sizeof(unsigned long long), hipMemcpyHostToDevice, stream));
-    DQ_HIP(hipStreamSynchronize(stream));
+    DQ_TRY(rollback_region_stage(nullptr));
     if (packed && h[FC_MAXLEN] <= 15) {
       // packed: the overflow list filled up, mostly with keys that are not digit strings -- this
       // table's keys are staged as 16-B records from now on (the packed regions are aggregated first)
@@ -586,20 +612,8 @@ struct dq_freq : Stager {
   // (the UUID regions already staged are aggregated first).
   dq_status stage_wide(int64_t n_rows, bool& staged_ok) {
     staged_ok = false;
-    if (staged > 0 && (!region_staged || region_wide != wide_keys)) DQ_TRY(materialize());
-    if (region_rows == 0 || staged + (uint64_t)n_rows > region_rows) {
-      if (staged > 0) DQ_TRY(materialize());
-      DQ_TRY(alloc_regions(std::max<uint64_t>((uint64_t)n_rows, reserve_rows)));
-    }
-    const uint64_t r1 = 1ull << kRegionBits;
+    DQ_TRY(begin_region_stage(n_rows, region_wide == wide_keys));
     unsigned long long* fill1 = static_cast<unsigned long long*>(d_pfill.ptr);
-    unsigned long long* save = fill1 + r1;
-    DQ_TRY(d_sketch_save.ensure(kHllM * sizeof(uint32_t) + sizeof(unsigned long long)));
-    uint8_t* sk_save = static_cast<uint8_t*>(d_sketch_save.ptr);
-    DQ_HIP(launch_freq_stage_save(fill1, save, (uint32_t)r1, static_cast<const uint32_t*>(d_sketch.ptr),
-                                  reinterpret_cast<uint32_t*>(sk_save), ctr() + FC_PART_OVF,
-                                  reinterpret_cast<unsigned long long*>(sk_save + kHllM * sizeof(uint32_t)),
-                                  ctr() + FC_MAXLEN, stream));
     DQ_HIP(hipMemsetAsync(ctr() + FC_UUID_BAD, 0, sizeof(unsigned long long), stream));
     region_packed = false;
     region_hashed = true;
@@ -622,14 +636,7 @@ struct dq_freq : Stager {
       staged_ok = true;
       return DQ_OK;
     }
-    // roll back: the fills, the sketch, the overflow count and the staged count as they were
-    DQ_HIP(hipMemcpyAsync(fill1, save, r1 * 8, hipMemcpyDeviceToDevice, stream));
-    DQ_HIP(hipMemcpyAsync(d_sketch.ptr, sk_save, kHllM * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
-    DQ_HIP(hipMemcpyAsync(ctr() + FC_PART_OVF, sk_save + kHllM * sizeof(uint32_t), sizeof(unsigned long long),
-                          hipMemcpyDeviceToDevice, stream));
-    DQ_HIP(hipMemsetAsync(ctr() + FC_PART_FLAG, 0, sizeof(unsigned long long), stream));
-    DQ_HIP(hipMemcpyAsync(ctr() + FC_STAGED, &staged, sizeof(unsigned long long), hipMemcpyHostToDevice, stream));
-    DQ_HIP(hipStreamSynchronize(stream));
+    DQ_TRY(rollback_region_stage(nullptr));
     if (debug)
       std::fprintf(stderr, "[dq_freq] %s staging rolled back (%llu other keys, flag %llu): hashed records from now on\n",
                    wide_keys == kRecUuid ? "uuid" : "16-byte", h[FC_UUID_BAD], h[FC_PART_FLAG]);
@@ -673,11 +680,7 @@ struct dq_freq : Stager {
       }
       if (wide_keys) return stage_wide(n_rows, staged_ok);
     }
-    if (staged > 0 && (!region_staged || !region_hashed || region_wide)) DQ_TRY(materialize());
-    if (region_rows == 0 || staged + (uint64_t)n_rows > region_rows) {
-      if (staged > 0) DQ_TRY(materialize());
-      DQ_TRY(alloc_regions(std::max<uint64_t>((uint64_t)n_rows, reserve_rows)));
-    }
+    DQ_TRY(begin_region_stage(n_rows, region_hashed && !region_wide));
     const DevColumn* dcols = static_cast<const DevColumn*>(d_cols.ptr);
     unsigned long long h0[FC_COUNT];
     DQ_TRY(read_counters(h0));
@@ -706,15 +709,7 @@ struct dq_freq : Stager {
         need = (uint64_t)((double)need * ((double)reserve_rows / (double)n_rows) * 1.02);
       DQ_TRY(ensure_heap(h0[FC_HEAP_USED], need));
     }
-    const uint64_t r1 = 1ull << kRegionBits;
     unsigned long long* fill1 = static_cast<unsigned long long*>(d_pfill.ptr);
-    unsigned long long* save = fill1 + r1;
-    DQ_TRY(d_sketch_save.ensure(kHllM * sizeof(uint32_t) + sizeof(unsigned long long)));
-    uint8_t* sk_save = static_cast<uint8_t*>(d_sketch_save.ptr);
-    DQ_HIP(launch_freq_stage_save(fill1, save, (uint32_t)r1, static_cast<const uint32_t*>(d_sketch.ptr),
-                                  reinterpret_cast<uint32_t*>(sk_save), ctr() + FC_PART_OVF,
-                                  reinterpret_cast<unsigned long long*>(sk_save + kHllM * sizeof(uint32_t)),
-                                  ctr() + FC_MAXLEN, stream));
     region_packed = false;
     region_hashed = true;
     DQ_TRY(d_rows.ensure((size_t)n_rows * sizeof(HashRec)));
@@ -733,16 +728,7 @@ struct dq_freq : Stager {
       staged_ok = true;
       return DQ_OK;
     }
-    // roll back: the fills, the sketch, the overflow count, the staged count and the heap cursor
-    DQ_HIP(hipMemcpyAsync(fill1, save, r1 * 8, hipMemcpyDeviceToDevice, stream));
-    DQ_HIP(hipMemcpyAsync(d_sketch.ptr, sk_save, kHllM * sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
-    DQ_HIP(hipMemcpyAsync(ctr() + FC_PART_OVF, sk_save + kHllM * sizeof(uint32_t), sizeof(unsigned long long),
-                          hipMemcpyDeviceToDevice, stream));
-    DQ_HIP(hipMemsetAsync(ctr() + FC_PART_FLAG, 0, sizeof(unsigned long long), stream));
-    DQ_HIP(hipMemcpyAsync(ctr() + FC_STAGED, &staged, sizeof(unsigned long long), hipMemcpyHostToDevice, stream));
-    DQ_HIP(hipMemcpyAsync(ctr() + FC_HEAP_USED, &h0[FC_HEAP_USED], sizeof(unsigned long long), hipMemcpyHostToDevice,
-                          stream));
-    DQ_HIP(hipStreamSynchronize(stream));
+    DQ_TRY(rollback_region_stage(&h0[FC_HEAP_USED]));  // (the heap cursor too)
     if (debug)
       std::fprintf(stderr, "[dq_freq] hashed staging rolled back (max len %llu, flag %llu)\n", h[FC_MAXLEN],
                    h[FC_PART_FLAG]);
@@ -1217,7 +1203,6 @@ extern "C" dq_status dq_freq_create(dq_ctx* ctx, const int32_t* key_columns, int
   if (const char* e = std::getenv("DQ_FREQ_HASHED")) f->hashed_enabled = e[0] != '0';  // A-B / test knob
   if (const char* e = std::getenv("DQ_FREQ_UUID")) f->uuid_enabled = e[0] != '0';  // A-B / test knob
   if (const char* e = std::getenv("DQ_FREQ_SMALL")) f->small_path = e[0] != '0';  // test / A-B knob
-  if (const char* e = std::getenv("DQ_FREQ_STAGE")) f->stage_rows = std::strcmp(e, "fused") != 0;  // A-B knob
   if (const char* e = std::getenv("DQ_FREQ_PART_LOAD")) {  // tuning knob
     const double v = std::atof(e);
     if (v >= 0.1 && v <= 0.95) f->part_load = v;

@@ -456,12 +456,19 @@ hipError_t launch_freq_small_flat(bool string_key, const FreqKeySpec& ks, const 
 hipError_t launch_freq_stage_save(const unsigned long long* d_fill, unsigned long long* d_fill_save, uint32_t n_fill,
                                   const uint32_t* d_sketch, uint32_t* d_sketch_save, const unsigned long long* d_ovf_n,
                                   unsigned long long* d_ovf_save, unsigned long long* d_long_key, hipStream_t stream);
-hipError_t launch_freq_stage_part(const FreqKeySpec& ks, bool one_string, bool packed, const DevColumn* d_cols,
-                                  int64_t n_rows, int b1, void* d_out,
-                                  uint64_t cap1, unsigned long long* d_fill1, FreqRec* d_ovf, unsigned long long* d_ovf_n,
-                                  uint64_t ovf_cap, unsigned int* d_flag, uint32_t* d_hll, unsigned long long* d_long_key,
-                                  unsigned long long* d_staged, hipStream_t stream,
-                                  void* d_rows = nullptr);
+// A batch staged into the level-1 regions d_out (b1 bits, cap1 records each, fills d_fill1).
+// Packed digit records of one utf8 key column: row-order staging into d_rows (n_rows words), then
+// the level-1 split over the rows.  16-byte FreqRecs (one_string: one utf8 key column): one kernel
+// that stages and splits.
+hipError_t launch_freq_stage_packed_rows(const FreqKeySpec& ks, const DevColumn* d_cols, int64_t n_rows, int b1,
+                                         uint64_t* d_rows, uint64_t* d_out, uint64_t cap1, unsigned long long* d_fill1,
+                                         FreqRec* d_ovf, unsigned long long* d_ovf_n, uint64_t ovf_cap, unsigned int* d_flag,
+                                         uint32_t* d_hll, unsigned long long* d_long_key, unsigned long long* d_staged,
+                                         hipStream_t stream);
+hipError_t launch_freq_stage_part(const FreqKeySpec& ks, bool one_string, const DevColumn* d_cols, int64_t n_rows, int b1,
+                                  FreqRec* d_out, uint64_t cap1, unsigned long long* d_fill1, FreqRec* d_ovf,
+                                  unsigned long long* d_ovf_n, uint64_t ovf_cap, unsigned int* d_flag, uint32_t* d_hll,
+                                  unsigned long long* d_long_key, unsigned long long* d_staged, hipStream_t stream);
 // The hashed partition path (dq_freq.hip, round 6).  Stage: every row's key (make_key: long
 // strings, several columns) is copied to the key heap (one atomic per wave) and written as a
 // HashRec in row order (holes for NULL keys); too_long: a multi-column key over kMaxLocalKey.

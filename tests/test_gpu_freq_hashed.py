@@ -14,7 +14,11 @@ each record of a hash group compared byte for byte with the group's first.  Chec
   reserved rows) and tables of fewer than 2^20 slots: the global inserts (exact, slower);
 * every operation after it (summary, top, export, lookup, merge, further batches).
 """
+import json
+import os
 import struct
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -25,6 +29,7 @@ from deequ_amd.frequencies import FrequencyTable, encode_key
 from helpers import oracle_table, product_table
 
 pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture
@@ -192,6 +197,55 @@ def test_composite_few_groups_many_rows(gpu):
     paths = t.paths()
     assert paths["hashed_runs"] == 0 and paths["wait_timeouts"] == 0, paths
     t.close()
+
+
+_UNROLLED_CHILD = r"""
+import collections, json
+import numpy as np
+import deequ_amd as d
+from deequ_amd.frequencies import FrequencyTable, encode_key
+
+d.set_device(0)
+lead, n = 8, 2 * 512 * 12 + 37  # (two full tiles of the string stages and a partial one; four hashed tiles)
+rng = np.random.default_rng(101)
+ids = rng.integers(0, 3000, n)
+a = [None if i % 67 == 5 else int(v % 700) - 350 for i, v in enumerate(ids)]
+b = [None if i % 67 == 40 else "name-%07d" % (v % 900) for i, v in enumerate(ids)]
+assert b[-1] is not None  # (the last key ends exactly at the values' last byte)
+
+
+def sliced(dtype, vals):  # rows [lead, lead + n) of a longer column: the bitmap starts at byte 1
+    c = d.Column.from_pylist([vals[-1]] * lead + vals, dtype)
+    return d.Column(dtype, n, c.values, c.validity, c.offsets, offset=lead)
+
+
+table = d.Table({"id": sliced("int64", a), "name": sliced("string", b)}).to_device(0)
+t = FrequencyTable(["id", "name"], dict(table.schema))
+t.reserve(n)
+t.consume(table)
+counts, keys = t.export()
+want = collections.Counter(encode_key([x, y], ["int64", "string"]) for x, y in zip(a, b)
+                           if x is not None and y is not None)
+print(json.dumps({"equal": dict(zip(keys, counts.tolist())) == dict(want), "groups": len(want),
+                  "hashed": t.paths()["hashed_runs"] + t.paths()["hashed_inserts"]}))
+t.close()
+"""
+
+
+def test_composite_keys_unrolled_stage(gpu):
+    """DQ_FREQ_HSTAGE=unrolled (read when the library loads, so a fresh process): the hashed
+    stage's unrolled body, dq_freq_stage_hashed_kernel<false>, on an (int64, utf8) key of 20+
+    encoded bytes.  12325 rows, 3 % NULLs, both columns sliced at row 8 (a validity bitmap at a byte
+    address that is no multiple of 4), the last key ending at the values' last byte.  Every group
+    and count against the Python count."""
+    env = dict(os.environ, DQ_FREQ_HSTAGE="unrolled", DQ_FREQ_PART_MIN="1", DQ_FREQ_PATH="sorted",
+               PYTHONPATH=os.pathsep.join([ROOT, os.path.join(ROOT, "oracle")]))
+    cmd = [sys.executable] + (["-s"] if sys.flags.no_user_site else []) + ["-c", _UNROLLED_CHILD]
+    r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
+    out = json.loads(r.stdout.splitlines()[-1])
+    # (hashed records were staged: aggregated in LDS, or -- a table of few slices -- inserted one by one)
+    assert out["equal"] and out["groups"] > 2000 and out["hashed"] >= 1, out
 
 
 # ---- canonical UUID keys (dq_uuidpack.h): the table stages each UUID as its 128 bits (UuidRec)
