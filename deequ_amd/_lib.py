@@ -135,6 +135,11 @@ class DqFreqDistance(Structure):
                 ("groups_b", c_int64), ("groups_common", c_int64)]
 
 
+class DqFreqMi(Structure):
+    _fields_ = [("mi", c_double), ("num_rows", c_int64), ("groups", c_int64), ("groups_a", c_int64),
+                ("groups_b", c_int64)]
+
+
 class DqFreqWire(Structure):
     _fields_ = [("ctrl", c_uint64), ("count", c_int64), ("k0", c_uint64), ("k1", c_uint64)]
 
@@ -202,6 +207,9 @@ DIAG_SIGNATURES = {
                                     POINTER(c_int64)]),
     "dq_diag_decimal_to_double": (c_int, [c_uint64, c_int64, c_int32, POINTER(c_double), POINTER(c_int32)]),
     "dq_diag_decimal_bytes": (c_int, [c_uint64, c_int64, c_char_p, POINTER(c_int32)]),
+    "dq_diag_mi_split": (c_int, [c_char_p, c_int64, c_int32, c_int32, POINTER(c_int32)]),
+    "dq_diag_mi_to_fixed": (c_int, [c_double, POINTER(c_uint64), POINTER(c_int64)]),
+    "dq_diag_mi_from_fixed": (c_int, [c_uint64, c_int64, POINTER(c_double)]),
     "dq_diag_plan_groups": (c_int, [c_void_p, POINTER(c_int64), c_int32, POINTER(c_int32), POINTER(c_int64)]),
     "dq_diag_plan_lanemask": (c_int, [c_void_p, POINTER(c_int32), c_int32, POINTER(c_int32)]),
 }
@@ -253,6 +261,7 @@ SIGNATURES = {
                             POINTER(c_int64), POINTER(c_int64)]),
     "dq_freq_merge": (c_int, [c_void_p, c_void_p]),
     "dq_freq_linf_distance": (c_int, [c_void_p, c_void_p, POINTER(DqFreqDistance)]),
+    "dq_freq_mutual_information": (c_int, [c_void_p, POINTER(DqFreqMi)]),
     "dq_freq_import": (c_int, [c_void_p, POINTER(DqFreqGroup), c_int64, c_void_p, c_int64]),
     "dq_freq_export_flat": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int,
                                     POINTER(c_int64), POINTER(c_int64)]),

@@ -806,11 +806,21 @@ class Entropy(ScanShareableFrequencyBasedAnalyzer):
         return "Entropy(%s)" % self.column
 
 
+# MutualInformation states of more joint groups than this are reduced on the device
+# (dq_freq_mutual_information).  Not a performance threshold: the reference's known answers are
+# asserted with == against what the host loop's libm log gives, and the device log may differ in the
+# last place, so small states keep the host loop and every result they had, bit for bit.
+MI_HOST_MAX_GROUPS = 4096
+
+
 @dataclass(frozen=True)
 class MutualInformation(FrequencyBasedAnalyzer):
     """Mutual information of two columns from their joint frequencies (MutualInformation.scala:
-    34-84).  The joint table is the GPU group-by; the marginals and the sum are taken over the
-    exported groups in a fixed (encoded-key) order."""
+    34-84).  The joint table is the GPU group-by.  A state of more than MI_HOST_MAX_GROUPS groups
+    held in one FrequencyTable is reduced where it lives (FrequencyTable.mutual_information: two
+    marginal tables and an exact, order-independent sum); smaller states and the per-owner states
+    of a sharded run take the marginals and the sum over the exported groups in a fixed
+    (encoded-key) order."""
     columns: tuple
     columnB: Optional[str] = field(default=None, compare=False, repr=False)  # MutualInformation(a, b)
     name = "MutualInformation"
@@ -833,7 +843,11 @@ class MutualInformation(FrequencyBasedAnalyzer):
         if state is None:
             return metric_from_failure(empty_state_exception(self), self.name, self.instance(), self.entity)
         import math
-        from .frequencies import decode_key
+        from .frequencies import FrequencyTable, decode_key
+        if isinstance(state.table, FrequencyTable) and state.summary().num_groups > MI_HOST_MAX_GROUPS:
+            # the marginals and the exact sum on the device: the joint table stays in HBM (a NaN
+            # from a group of count 0 is the metric's value, as on the JVM)
+            return metric_from_value(state.table.mutual_information().mi, self.name, self.instance(), self.entity)
         total = state.numRows
         counts, keys = state.table.export()
         if len(keys) == 0:

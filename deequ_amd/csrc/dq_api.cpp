@@ -26,6 +26,7 @@
 #include "dq_uuidpack.h"
 #include "dq_numparse.h"
 #include "dq_decimal.h"
+#include "dq_mi.h"
 #include "dq_predeval.h"
 #include "dq_regex.h"
 #include "dq_kll.h"
@@ -2321,6 +2322,45 @@ extern "C" dq_status dq_diag_decimal_bytes(uint64_t lo, int64_t hi, uint8_t* out
   const dec::u128 st = dec::be_stream(lo, hi, n);
   for (int j = 0; j < n; ++j) out[j] = (uint8_t)(st >> (8 * j));
   *len = n;
+  return DQ_OK;
+}
+
+// Host build of MutualInformation's key split and fixed-point conversions (dq_mi.h, the source the
+// kernels run on the device).
+namespace {
+struct HostKey {  // a joint key's bytes for mi::split (u32 is only asked for bytes inside the key)
+  const uint8_t* p;
+  uint32_t u32(uint32_t off) const {
+    return (uint32_t)p[off] | ((uint32_t)p[off + 1] << 8) | ((uint32_t)p[off + 2] << 16) | ((uint32_t)p[off + 3] << 24);
+  }
+};
+static_assert(mi::kTypeUtf8 == DQ_T_UTF8, "dq_mi.h names DQ_T_UTF8 by value");
+}  // namespace
+
+extern "C" dq_status dq_diag_mi_split(const uint8_t* key, int64_t len, int32_t type_a, int32_t type_b, int32_t* out) {
+  if ((!key && len > 0) || !out || len < 0 || len > (int64_t)0xFFFFFF) return fail(DQ_ERR_INVALID, "bad argument");
+  mi::Split s;
+  if (!mi::split(HostKey{key}, (uint32_t)len, type_a, type_b, &s))
+    return fail(DQ_ERR_INVALID, "the key does not split into the two key column types");
+  out[0] = (int32_t)s.off_a;
+  out[1] = (int32_t)s.len_a;
+  out[2] = (int32_t)s.off_b;
+  out[3] = (int32_t)s.len_b;
+  return DQ_OK;
+}
+
+extern "C" dq_status dq_diag_mi_to_fixed(double term, uint64_t* lo, int64_t* hi) {
+  if (!lo || !hi) return fail(DQ_ERR_INVALID, "bad argument");
+  mi::i128 v;
+  if (!mi::to_fixed(term, &v)) return fail(DQ_ERR_INVALID, "the term is not finite or not below 2^6 in magnitude");
+  *lo = (uint64_t)v;
+  *hi = (int64_t)(v >> 64);
+  return DQ_OK;
+}
+
+extern "C" dq_status dq_diag_mi_from_fixed(uint64_t lo, int64_t hi, double* out) {
+  if (!out) return fail(DQ_ERR_INVALID, "bad argument");
+  *out = mi::from_fixed((mi::i128)(((mi::u128)(uint64_t)hi << 64) | (mi::u128)lo));
   return DQ_OK;
 }
 

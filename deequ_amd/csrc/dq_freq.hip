@@ -22,6 +22,7 @@
 // cost one global atomic per (workgroup, key) instead of one per row.
 #include "dq_internal.h"
 #include "dq_keypack.h"
+#include "dq_mi.h"
 #include "dq_uuidpack.h"
 
 #include <cstdio>
@@ -374,7 +375,9 @@ __device__ bool heap_equal(const FreqTable& T, uint64_t off, const uint8_t* p, u
 // hands such rows back for a retry after the table grows).
 // kKeyInHeap: a long key's bytes already lie in T's heap at k.ptr (the hashed path's stage put
 // them there): a claimed slot refers to them instead of copying them again.
-template <bool kFlagOverflow = true, bool kKeyInHeap = false>
+// kCountGroups = false: a claimed slot is not added to T.n_groups (one word that every new group
+// of every workgroup would add to; the caller counts the occupied slots afterwards).
+template <bool kFlagOverflow = true, bool kKeyInHeap = false, bool kCountGroups = true>
 __device__ bool global_insert(const FreqTable& T, const Key& k, unsigned long long cnt) {
   // Every action happens inside the loop iteration and the loop ends only through `state`: a
   // lane that waits for another lane of its own wave to publish a slot must see that publish in
@@ -415,7 +418,7 @@ __device__ bool global_insert(const FreqTable& T, const Key& k, unsigned long lo
         }
       }
       atomicAdd(&e->count, cnt);
-      if (heap_ok) atomicAdd(T.n_groups, 1ull);
+      if (heap_ok && kCountGroups) atomicAdd(T.n_groups, 1ull);
       if (!(T.test_flags & kFreqTestNoPublish))
         __hip_atomic_fetch_or(&e->ctrl, kReady, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
       state = heap_ok ? 1 : 3;  // (3: heap full, flagged above with bit 2 only)
@@ -1007,6 +1010,285 @@ __global__ __launch_bounds__(kBlock) void dq_freq_linf_kernel(FreqTable X, FreqT
     }
     if (m) atomicMax(out_max, m);
     if (out_common && c) atomicAdd(out_common, c);
+  }
+}
+
+// ---- MutualInformation (MutualInformation.scala:38-81) over a joint table X of two key columns:
+//   sum over the joint groups of (pxy / total) * log((pxy / total) / ((px / total) * (py / total)))
+// with px / py the sums of the joint counts over each value of key column 0 / 1.  X stays as it
+// is; two passes read its slot image (launch boundary: every insert is visible):
+//  1. projection: every occupied slot splits its key bytes into the two fields (dq_mi.h), re-encodes
+//     each as a single-column key (<= 16 bytes: inline words hashed by hash_inline; longer: a
+//     reference to its bytes in X's heap, hashed by hash_long) and adds its count to two scratch
+//     marginal tables TA / TB -- ordinary FreqTables filled by global_insert.  A joint table over
+//     (id, category) sends every group's count to a handful of marginal slots, so a workgroup
+//     first aggregates in LDS: one 512-slot table per marginal with 64-bit counts (joint counts
+//     are 64-bit and a workgroup's partial sum can pass 2^32), flushed with one global_insert per
+//     (workgroup, key).  A long field is held there as {offset of the first equal field seen in
+//     X's heap, its table hash} and compared by its bytes.  A marginal whose keys keep missing the
+//     LDS table (a high-cardinality column) stops probing it.  The inserts do not count groups
+//     (T.n_groups would be one word that 10^7 new groups add to): the host counts the marginals'
+//     occupied slots with dq_freq_totals_kernel, whose sums of counts must both equal the joint's.
+//  2. sum: every occupied slot rebuilds its two field keys, probes TA and TB as dq_freq_linf_kernel
+//     probes Y, forms its term in fp64 in the reference's operation order and converts it to
+//     signed fixed point with 96 fraction bits (mi::to_fixed: one rounding rule).  The integers
+//     add exactly: 128-bit wave reduction by shuffles, the four waves through LDS, one pair of
+//     64-bit atomics per workgroup (low word, then the high word plus the low word's carry), so
+//     the sum is the same for every slot order, capacity and schedule.  A term that is NaN (a
+//     group of count 0: 0 * -inf, or log(NaN)) raises a flag word and stays out of the sum.
+// Both loops run whole workgroups past the last slot together, as the Distance kernels do.
+constexpr int kMiLdsHalf = 512;           // LDS pre-aggregation slots per marginal
+
+// A joint key's bytes: its slot's inline words, or (p != nullptr) its bytes in the heap.
+struct MiKeyBytes {
+  uint64_t k0, k1;
+  const uint8_t* p;
+  __device__ uint32_t u32(uint32_t off) const {  // off + 4 <= the key's length
+    if (p) return (uint32_t)ld_partial(p + off, 4);
+    const mi::u128 v = ((mi::u128)k1 << 64) | (mi::u128)k0;
+    return (uint32_t)(v >> (8u * off));
+  }
+  // bytes off .. off + n (n <= 16) as a single-column key's inline words
+  __device__ void words(uint32_t off, uint32_t n, uint64_t& a, uint64_t& b) const {
+    if (p) {
+      a = ld_partial(p + off, n < 8u ? n : 8u);
+      b = n > 8u ? ld_partial(p + off + 8, n - 8u) : 0ull;
+      return;
+    }
+    mi::u128 v = 0;  // (off <= 16; an empty field may start at the key's end)
+    if (off < 16u) v = (((mi::u128)k1 << 64) | (mi::u128)k0) >> (8u * off);
+    if (n < 16u) v &= (((mi::u128)1) << (8u * n)) - 1;
+    a = (uint64_t)v;
+    b = (uint64_t)(v >> 64);
+  }
+};
+
+__device__ inline Key mi_field_key(const MiKeyBytes& kb, uint32_t off, uint32_t n) {
+  Key k;
+  k.k0 = k.k1 = 0;
+  k.ptr = nullptr;
+  k.len = n;
+  if (n <= 16u) {
+    kb.words(off, n, k.k0, k.k1);
+    k.hash = hash_inline(k.k0, k.k1, n);
+  } else {  // (a field of more than 16 bytes lies in a heap key)
+    k.ptr = kb.p + off;
+    k.hash = hash_long(k.ptr, n);
+  }
+  return k;
+}
+
+// Slot s of X as its two field keys: 0 = no group there, 1 = a group, 2 = a group whose key cannot
+// be read (it does not split into the two column types, or its heap reference points past the
+// heap and is not followed).
+__device__ inline int mi_load(const FreqTable& X, uint64_t s, uint64_t n_slots, int type_a, int type_b, Key& a,
+                              Key& b, unsigned long long& count) {
+  FreqSlot e{};
+  if (s < n_slots) e = X.slots[s];
+  if (!(e.ctrl & kReady)) return 0;
+  const uint32_t len = (uint32_t)(e.ctrl & kLenMask);
+  const bool heap = (e.ctrl & kHeapKey) != 0;
+  if (heap && (e.k0 > X.heap_cap || (unsigned long long)len > X.heap_cap - e.k0)) return 2;
+  if (!heap && len > 16u) return 2;
+  const MiKeyBytes kb{e.k0, e.k1, heap ? X.heap + e.k0 : nullptr};
+  mi::Split sp;
+  if (!mi::split(kb, len, type_a, type_b, &sp)) return 2;
+  a = mi_field_key(kb, sp.off_a, sp.len_a);
+  b = mi_field_key(kb, sp.off_b, sp.len_b);
+  count = e.count;
+  return 1;
+}
+
+__device__ inline bool mi_bytes_equal(const uint8_t* p, const uint8_t* q, uint32_t len) {
+  for (uint32_t j = 0; j < len; j += 8) {
+    const uint32_t n = len - j < 8 ? len - j : 8;
+    if (ld_partial(p + j, n) != ld_partial(q + j, n)) return false;
+  }
+  return true;
+}
+
+struct MiLds {  // structure of arrays, as LdsTable; slots [h * kMiLdsHalf, (h + 1) * kMiLdsHalf) hold marginal h
+  unsigned long long ctrl[2 * kMiLdsHalf];  // tag(32) << 32 | READY | HEAP | len; 1 = being published
+  unsigned long long k0[2 * kMiLdsHalf], k1[2 * kMiLdsHalf];  // inline words, or {offset in X's heap, table hash}
+  unsigned long long count[2 * kMiLdsHalf];
+};
+
+// Adds cnt to key k's group in marginal `half`'s LDS table (claiming a slot for a new key);
+// false when the probes found no room or kept meeting a slot that another lane is publishing.
+__device__ inline bool mi_lds_add(MiLds* L, int half, const uint8_t* heap, const Key& k, unsigned long long cnt) {
+  const bool inl = k.len <= 16u;
+  const unsigned long long a = inl ? k.k0 : (unsigned long long)(k.ptr - heap);
+  const unsigned long long b = inl ? k.k1 : k.hash;
+  const uint32_t lh = (uint32_t)(k.hash >> 32) ^ (uint32_t)k.hash;
+  const unsigned long long want = ((unsigned long long)lh << 32) | kReady | (inl ? 0ull : kHeapKey) | k.len;
+  const uint32_t base = (uint32_t)half * kMiLdsHalf;
+  uint32_t s = lh & (kMiLdsHalf - 1);
+  for (int probe = 0; probe < kLdsProbe * 4;) {
+    const uint32_t i = base + s;
+    unsigned long long c = __hip_atomic_load(&L->ctrl[i], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (c == 0ull) c = atomicCAS(&L->ctrl[i], 0ull, 1ull);
+    if (c == 0ull) {  // claimed: key, count, then the ctrl word that publishes them
+      L->k0[i] = a;
+      L->k1[i] = b;
+      atomicAdd(&L->count[i], cnt);
+      __threadfence_block();
+      atomicExch(&L->ctrl[i], want);
+      return true;
+    }
+    if (c == 1ull) {
+      ++probe;  // another lane is publishing this slot: look again
+      continue;
+    }
+    if (c == want) {
+      const unsigned long long y0 = __hip_atomic_load(&L->k0[i], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
+      const unsigned long long y1 = __hip_atomic_load(&L->k1[i], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP);
+      const bool eq = inl ? (y0 == a && y1 == b) : (y1 == b && mi_bytes_equal(heap + y0, k.ptr, k.len));
+      if (eq) {
+        atomicAdd(&L->count[i], cnt);
+        return true;
+      }
+    }
+    s = (s + 1) & (kMiLdsHalf - 1);
+    probe += 4;
+  }
+  return false;
+}
+
+__global__ __launch_bounds__(kBlock) void dq_mi_project_kernel(FreqTable X, FreqTable TA, FreqTable TB, int type_a,
+                                                               int type_b, unsigned int* flags) {
+  __shared__ MiLds lds;
+  __shared__ unsigned int lds_misses[2];  // inserts that found no room: 2 * kMiLdsHalf of them close the table
+  for (int i = threadIdx.x; i < 2 * kMiLdsHalf; i += kBlock) {
+    lds.ctrl[i] = 0;
+    lds.count[i] = 0;
+  }
+  if (threadIdx.x < 2) lds_misses[threadIdx.x] = 0u;
+  __syncthreads();
+  const uint64_t n_slots = X.mask + 1;
+  unsigned int fl = 0u;
+  for (uint64_t base = (uint64_t)blockIdx.x * kBlock; base < n_slots; base += (uint64_t)gridDim.x * kBlock) {
+    Key k[2];
+    unsigned long long count = 0;
+    const int st = mi_load(X, base + threadIdx.x, n_slots, type_a, type_b, k[0], k[1], count);
+    if (st == 2) fl |= kMiBadKey;
+    if (st != 1) continue;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      bool done = false;
+      if (__hip_atomic_load(&lds_misses[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < 2u * kMiLdsHalf) {
+        done = mi_lds_add(&lds, h, X.heap, k[h], count);
+        if (!done) atomicAdd(&lds_misses[h], 1u);  // (full of other keys: this marginal soon stops probing LDS)
+      }
+      if (!done && !global_insert<true, false, false>(h ? TB : TA, k[h], count)) fl |= kMiNoGroup;
+    }
+  }
+  __syncthreads();
+  for (int i = threadIdx.x; i < 2 * kMiLdsHalf; i += kBlock) {
+    const unsigned long long c = lds.ctrl[i];
+    if (c <= 1ull) continue;
+    Key k;
+    k.len = (uint32_t)(c & kLenMask);
+    if (c & kHeapKey) {
+      k.k0 = k.k1 = 0;
+      k.ptr = X.heap + lds.k0[i];
+      k.hash = lds.k1[i];
+    } else {
+      k.k0 = lds.k0[i];
+      k.k1 = lds.k1[i];
+      k.ptr = nullptr;
+      k.hash = hash_inline(k.k0, k.k1, k.len);
+    }
+    if (!global_insert<true, false, false>(i >= kMiLdsHalf ? TB : TA, k, lds.count[i])) fl |= kMiNoGroup;
+  }
+  if (fl) atomicOr(flags, fl);
+}
+
+// The count of key k's group in T (plain loads: T was filled by an earlier launch).
+__device__ inline bool mi_probe(const FreqTable& T, const Key& k, unsigned long long& count) {
+  const uint32_t tag = tag_of(k.hash);
+  const bool heap = k.len > 16u;
+  const unsigned long long form = (heap ? kHeapKey : 0ull) | k.len;
+  for (uint64_t i = 0; i < kFreqSliceSlots; ++i) {
+    const FreqSlot y = T.slots[probe_slot(T, k.hash, i)];
+    if (y.ctrl == 0ull) return false;
+    if ((uint32_t)(y.ctrl >> 32) != tag || (y.ctrl & (kLenMask | kHeapKey)) != form) continue;
+    bool eq;
+    if (!heap) eq = y.k0 == k.k0 && y.k1 == k.k1;
+    else eq = y.k0 <= T.heap_cap && (unsigned long long)k.len <= T.heap_cap - y.k0 && mi_bytes_equal(T.heap + y.k0, k.ptr, k.len);
+    if (eq) {
+      count = y.count;
+      return true;
+    }
+  }
+  return false;
+}
+
+// One group's term, in the reference's operation order (each operation one IEEE fp64 rounding:
+// no contraction, no reassociation).
+__device__ inline double mi_term(unsigned long long cxy, unsigned long long cx, unsigned long long cy, double total) {
+#pragma clang fp contract(off)
+  const double pxy = (double)cxy, px = (double)cx, py = (double)cy;
+  const double p = pxy / total;
+  const double ratio = p / ((px / total) * (py / total));
+  return p * log(ratio);
+}
+
+__device__ inline mi::i128 wave_sum_i128(mi::i128 v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long lo = __shfl_xor((unsigned long long)v, o);
+    const unsigned long long hi = __shfl_xor((unsigned long long)((mi::u128)v >> 64), o);
+    v += (mi::i128)(((mi::u128)hi << 64) | (mi::u128)lo);
+  }
+  return v;
+}
+
+// out[0], out[1] += the low / high words of the sum of the fixed-point terms, out[2] |= flags.
+__global__ __launch_bounds__(kBlock) void dq_mi_sum_kernel(FreqTable X, FreqTable TA, FreqTable TB, int type_a, int type_b,
+                                                           double total, unsigned long long* out) {
+  __shared__ unsigned long long part[kBlock / 64][3];
+  const uint64_t n_slots = X.mask + 1;
+  mi::i128 acc = 0;
+  unsigned int fl = 0u;
+  for (uint64_t base = (uint64_t)blockIdx.x * kBlock; base < n_slots; base += (uint64_t)gridDim.x * kBlock) {
+    Key a, b;
+    unsigned long long cxy = 0, cx = 0, cy = 0;
+    const int st = mi_load(X, base + threadIdx.x, n_slots, type_a, type_b, a, b, cxy);
+    if (st == 2) fl |= kMiBadKey;
+    if (st != 1) continue;
+    if (!mi_probe(TA, a, cx) || !mi_probe(TB, b, cy)) {
+      fl |= kMiNoGroup;
+      continue;
+    }
+    mi::i128 fx;
+    if (mi::to_fixed(mi_term(cxy, cx, cy, total), &fx)) acc += fx;
+    else fl |= kMiNanTerm;
+  }
+  acc = wave_sum_i128(acc);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) fl |= (unsigned int)__shfl_xor((int)fl, o);
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) {
+    part[wave][0] = (unsigned long long)acc;
+    part[wave][1] = (unsigned long long)((mi::u128)acc >> 64);
+    part[wave][2] = fl;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    mi::u128 sum = 0;
+    unsigned long long f = 0;
+    for (int w = 0; w < kBlock / 64; ++w) {
+      sum += ((mi::u128)part[w][1] << 64) | (mi::u128)part[w][0];
+      f |= part[w][2];
+    }
+    const unsigned long long lo = (unsigned long long)sum;
+    unsigned long long hi = (unsigned long long)(sum >> 64);
+    if (lo) {  // the low word's carry goes with this workgroup's high word
+      const unsigned long long old = atomicAdd(&out[0], lo);
+      if (old + lo < old) hi += 1ull;
+    }
+    if (hi) atomicAdd(&out[1], hi);
+    if (f) atomicOr(&out[2], f);
   }
 }
 
@@ -4708,6 +4990,20 @@ hipError_t launch_freq_linf(const FreqTable& X, const FreqTable& Y, double nx, d
                             unsigned long long* d_common, hipStream_t stream) {
   hipLaunchKernelGGL(dq_freq_linf_kernel, dim3(freq_dist_blocks(X)), dim3(kBlock), 0, stream, X, Y, nx, ny, d_max,
                      d_common);
+  return hipGetLastError();
+}
+
+hipError_t launch_freq_mi_project(const FreqTable& X, const FreqTable& TA, const FreqTable& TB, int type_a, int type_b,
+                                  unsigned int* d_flags, hipStream_t stream) {
+  hipLaunchKernelGGL(dq_mi_project_kernel, dim3(freq_dist_blocks(X)), dim3(kBlock), 0, stream, X, TA, TB, type_a, type_b,
+                     d_flags);
+  return hipGetLastError();
+}
+
+hipError_t launch_freq_mi_sum(const FreqTable& X, const FreqTable& TA, const FreqTable& TB, int type_a, int type_b,
+                              double total, unsigned long long* d_out, hipStream_t stream) {
+  hipLaunchKernelGGL(dq_mi_sum_kernel, dim3(freq_dist_blocks(X)), dim3(kBlock), 0, stream, X, TA, TB, type_a, type_b, total,
+                     d_out);
   return hipGetLastError();
 }
 

@@ -2015,6 +2015,89 @@ extern "C" dq_status dq_freq_linf_distance(dq_freq* a, dq_freq* b, dq_freq_dista
   return DQ_OK;
 }
 
+// MutualInformation over one device state of two key columns (MutualInformation.scala:38-81): see
+// dq_freq.hip "MutualInformation".  Words of f->d_dist: {f's lo / hi / groups (totals), the first
+// marginal's groups (unused) / heap use / overflow, the second's, the sum's low / high word, its
+// flags, the first marginal's lo / hi / groups (totals), the second's}.
+// The marginal tables are scratch: sized for f's groups and heap use (no growth, no retry) and
+// released on return.
+extern "C" dq_status dq_freq_mutual_information(dq_freq* f, dq_freq_mi* out) {
+  if (!f) return fail(DQ_ERR_INVALID, "NULL table");
+  if (!out) return fail(DQ_ERR_INVALID, "NULL argument");
+  if (f->ks.n_keys != 2) return fail(DQ_ERR_INVALID, "MutualInformation needs a table that groups exactly two key columns");
+  if (f->ks.null_as_key) return fail(DQ_ERR_INVALID, "MutualInformation is not defined over a Histogram (NULL-as-key) table");
+  const int type_a = f->col_types[f->ks.key_cols[0]], type_b = f->col_types[f->ks.key_cols[1]];
+  DQ_HIP(hipSetDevice(f->ctx->device));
+  DQ_TRY(f->materialize());
+  unsigned long long h[FC_COUNT];
+  DQ_TRY(f->read_counters(h));
+  dq_freq_mi r{};
+  r.mi = std::numeric_limits<double>::quiet_NaN();
+  r.num_rows = f->num_rows;
+  if (h[FC_GROUPS] == 0) {  // (the analyzer reports the empty state)
+    *out = r;
+    return DQ_OK;
+  }
+  if (f->num_rows < 0 || f->num_rows > ((int64_t)1 << 53))
+    return fail(DQ_ERR_UNSUPPORTED, "the table's numRows is above 2^53: not exact as the fp64 total of the reference");
+  constexpr int kWords = 18;
+  DQ_TRY(f->d_dist.ensure(kWords * sizeof(unsigned long long)));
+  unsigned long long* d = static_cast<unsigned long long*>(f->d_dist.ptr);
+  unsigned long long w[kWords] = {};
+  DQ_HIP(hipMemsetAsync(d, 0, sizeof(w), f->stream));
+  DQ_HIP(launch_freq_totals(f->view(), d, f->stream));
+  DQ_HIP(hipMemcpyAsync(w, d, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, f->stream));
+  DQ_HIP(hipStreamSynchronize(f->stream));
+  const unsigned __int128 n = ((unsigned __int128)w[1] << 32) + w[0];
+  r.groups = (int64_t)w[2];
+  if (r.groups == 0) {
+    *out = r;
+    return DQ_OK;
+  }
+  if (n > (unsigned __int128)f->num_rows)
+    return fail(DQ_ERR_UNSUPPORTED, "the table's counts sum to more than its numRows: a probability above 1 has no bounded term");
+  uint64_t cap = kFreqSliceSlots;
+  while (cap < 2 * (uint64_t)r.groups) cap <<= 1;
+  DevBuf slots[2], heap[2];
+  FreqTable T[2];
+  for (int i = 0; i < 2; ++i) {
+    DQ_TRY(slots[i].ensure(cap * sizeof(FreqSlot)));
+    DQ_TRY(heap[i].ensure((size_t)h[FC_HEAP_USED] + 8));
+    DQ_HIP(hipMemsetAsync(slots[i].ptr, 0, cap * sizeof(FreqSlot), f->stream));
+    T[i].slots = static_cast<FreqSlot*>(slots[i].ptr);
+    T[i].mask = cap - 1;
+    T[i].bucket_bits = slice_bits_for(cap);
+    T[i].test_flags = 0;
+    T[i].n_groups = d + 3 + 3 * i;
+    T[i].heap = static_cast<uint8_t*>(heap[i].ptr);
+    T[i].heap_used = d + 4 + 3 * i;
+    T[i].heap_cap = heap[i].cap;
+    T[i].overflow = reinterpret_cast<unsigned int*>(d + 5 + 3 * i);
+  }
+  const FreqTable X = f->view();
+  DQ_HIP(launch_freq_mi_project(X, T[0], T[1], type_a, type_b, reinterpret_cast<unsigned int*>(d + 11), f->stream));
+  DQ_HIP(launch_freq_mi_sum(X, T[0], T[1], type_a, type_b, (double)f->num_rows, d + 9, f->stream));
+  DQ_HIP(launch_freq_totals(T[0], d + 12, f->stream));
+  DQ_HIP(launch_freq_totals(T[1], d + 15, f->stream));
+  DQ_HIP(hipMemcpyAsync(w, d, sizeof(w), hipMemcpyDeviceToHost, f->stream));
+  DQ_HIP(hipStreamSynchronize(f->stream));  // (the scratch tables are released below: the stream is idle)
+  const unsigned int flags = (unsigned int)w[11];
+  if (flags & kMiBadKey) return fail(DQ_ERR_INVALID, "a group key does not split into the table's two key columns");
+  if ((flags & kMiNoGroup) || (unsigned int)w[5] || (unsigned int)w[8])
+    return fail(DQ_ERR_DEVICE, "MutualInformation: a marginal group could not be placed or found (internal)");
+  for (int i = 0; i < 2; ++i)  // every joint count went to exactly one group of either marginal
+    if ((((unsigned __int128)w[13 + 3 * i] << 32) + w[12 + 3 * i]) != n)
+      return fail(DQ_ERR_DEVICE, "MutualInformation: a marginal table's counts do not sum to the joint table's (internal)");
+  r.groups_a = (int64_t)w[14];
+  r.groups_b = (int64_t)w[17];
+  if (!(flags & kMiNanTerm)) {
+    const mi::u128 sum = ((mi::u128)w[10] << 64) | (mi::u128)w[9];
+    r.mi = mi::from_fixed((mi::i128)sum);
+  }
+  *out = r;
+  return DQ_OK;
+}
+
 // ---------------------------------------------------------------- multi-GPU key-hash exchange
 extern "C" dq_status dq_freq_partition(dq_freq* f, int n_parts, void* d_out, int64_t out_bytes, uint8_t* d_key_bytes,
                                        int64_t key_cap, int64_t* part_packed, int64_t* part_groups,

@@ -391,6 +391,18 @@ constexpr unsigned kFreqDistMaxBlocks = 2048;  // the passes' grid cap (kBlock s
 hipError_t launch_freq_totals(const FreqTable& T, unsigned long long* d_tot, hipStream_t stream);
 hipError_t launch_freq_linf(const FreqTable& X, const FreqTable& Y, double nx, double ny, unsigned long long* d_max,
                             unsigned long long* d_common, hipStream_t stream);
+// MutualInformation (dq_freq_mutual_information, dq_freq.hip "MutualInformation") over the joint
+// table X of two key columns of types type_a / type_b (DQ_T_*).  project: every group of X adds its
+// count to its two fields' groups in the empty marginal tables TA / TB; *d_flags |= kMiBadKey /
+// kMiNoGroup.  sum: d_out[0], d_out[1] += the low / high words of the 128-bit sum of the groups'
+// terms in fixed point (dq_mi.h), d_out[2] |= kMiNanTerm / kMiBadKey / kMiNoGroup.
+constexpr unsigned int kMiNanTerm = 1u;   // a term was not finite (the metric is NaN)
+constexpr unsigned int kMiBadKey = 2u;    // a key that does not split, or a heap reference past the heap
+constexpr unsigned int kMiNoGroup = 4u;   // a field without its marginal group, or no room for it (internal)
+hipError_t launch_freq_mi_project(const FreqTable& X, const FreqTable& TA, const FreqTable& TB, int type_a, int type_b,
+                                  unsigned int* d_flags, hipStream_t stream);
+hipError_t launch_freq_mi_sum(const FreqTable& X, const FreqTable& TA, const FreqTable& TB, int type_a, int type_b,
+                              double total, unsigned long long* d_out, hipStream_t stream);
 hipError_t launch_freq_heap_need(const FreqKeySpec& ks, const DevColumn* d_cols, int64_t n_rows,
                                  unsigned long long* d_need, unsigned long long* d_max_len, hipStream_t stream);
 // Sorted-bucket path (dq_freq.hip): stage rows as FreqRec + an HLL sketch of their hashes (to size

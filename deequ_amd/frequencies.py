@@ -6,8 +6,10 @@ Replaces `FrequencyBasedAnalyzer.computeFrequencies` (analyzers/GroupingAnalyzer
 
 and the group-by of `Histogram.computeStateFrom` (Histogram.scala:54-69).  The table lives in
 HBM (an open-addressing hash table built by deequ_amd/csrc/dq_freq.hip); the metrics of the
-frequency family are derived on the device from a count-of-counts histogram, so a 200M-group
-table never leaves the GPU unless the caller exports it (state persistence, Spark interop).
+frequency family are derived on the device from a count-of-counts histogram (MutualInformation:
+from two marginal tables projected out of the joint one, FrequencyTable.mutual_information), so
+a 200M-group table never leaves the GPU unless the caller exports it (state persistence, Spark
+interop).
 
 Group keys cross the C-ABI in an encoded form (see include/deequ_amd.h): fixed-width values
 as their little-endian bytes (floats as raw bits -- Spark 2.2 groups by the UnsafeRow bytes),
@@ -316,6 +318,14 @@ class FrequencyTable:
         the group counts (dq_freq_linf_distance), device to device; neither table changes."""
         out = L.DqFreqDistance()
         L.check(L.lib().dq_freq_linf_distance(self.handle, other.handle, ctypes.byref(out)))
+        return out
+
+    def mutual_information(self) -> L.DqFreqMi:
+        """MutualInformation of this table's two key columns with numRows and the joint and
+        marginal group counts (dq_freq_mutual_information): the marginals and the exact sum are
+        taken on the device; the table does not change."""
+        out = L.DqFreqMi()
+        L.check(L.lib().dq_freq_mutual_information(self.handle, ctypes.byref(out)))
         return out
 
     def close(self) -> None:

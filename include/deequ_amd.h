@@ -528,6 +528,25 @@ typedef struct dq_freq_distance {
   int64_t groups_a, groups_b, groups_common;
 } dq_freq_distance;
 dq_status dq_freq_linf_distance(dq_freq* a, dq_freq* b, dq_freq_distance* out);
+/* MutualInformation over one state of two key columns (MutualInformation.scala:38-81), on the
+ * device: mi = the sum over the joint groups of (pxy / total) * log((pxy / total) / ((px / total) *
+ * (py / total))), total = (double)num_rows (rows with a NULL key included), px / py the sums of the
+ * joint counts over each value of key column 0 / 1, every operation one IEEE fp64 operation in that
+ * order.  The terms are added exactly (128-bit fixed point, 96 fraction bits, each term rounded to
+ * nearest-even once) and the sum is rounded to fp64 once, so mi does not depend on the order of
+ * the groups: a merged state and the union of its rows give the same bits.  The table must group
+ * exactly two key columns (they may be the same column) and not be a DQ_FREQ_NULL_AS_KEY table
+ * (DQ_ERR_INVALID).  No groups: DQ_OK, mi = NaN, the group counts 0.  A group of count 0 makes its
+ * term 0 * -inf or log(NaN): mi = NaN, as on the JVM.  num_rows above 2^53, or below the sum of
+ * the counts, is DQ_ERR_UNSUPPORTED.  The table does not change. */
+typedef struct dq_freq_mi {
+  double  mi;         /* sum over the joint groups                                */
+  int64_t num_rows;   /* the state's numRows (`total` of the reference)           */
+  int64_t groups;     /* joint groups                                             */
+  int64_t groups_a;   /* distinct values of key column 0 among the groups         */
+  int64_t groups_b;   /* ... of key column 1                                      */
+} dq_freq_mi;
+dq_status dq_freq_mutual_information(dq_freq* f, dq_freq_mi* out);
 /* Merge groups (and `num_rows`) into the table: FrequenciesAndNumRows.sum. */
 /* Count of one group (0 if the key is absent), key in the encoded form above.  Used to fold a
  * literal "NullValue" string into Histogram's NULL bin when Histogram shares the frequency

@@ -122,6 +122,20 @@ dq_status dq_diag_decimal_to_double(uint64_t lo, int64_t hi, int32_t scale, doub
  * (java.math.BigInteger.toByteArray of the unscaled value): out[0 .. *len), *len in 1..16. */
 dq_status dq_diag_decimal_bytes(uint64_t lo, int64_t hi, uint8_t* out, int32_t* len);
 
+/* Host build of MutualInformation's shared source (deequ_amd/csrc/dq_mi.h, the code the kernels
+ * behind dq_freq_mutual_information run on the device).
+ * dq_diag_mi_split: the joint key key[0 .. len) of two key columns of types type_a / type_b (DQ_T_*)
+ * -> out[0..3] = {offset, length of the first field, offset, length of the second}: a fixed-width
+ * field is its bytes, a string field its UTF-8 bytes without the u32 length prefix.  A key that
+ * does not split exactly (a length running past the key, a truncated fixed field, bytes left
+ * over, a type that is no key type) is DQ_ERR_INVALID; no byte at or past `len` is read.
+ * dq_diag_mi_to_fixed: a term as the signed 128-bit integer round-half-even(|term| 2^96) with the
+ * term's sign (*lo, *hi = its two's-complement words); NaN, infinities and |term| >= 2^6 are
+ * DQ_ERR_INVALID.  dq_diag_mi_from_fixed: the nearest double (ties to even) of that integer / 2^96. */
+dq_status dq_diag_mi_split(const uint8_t* key, int64_t len, int32_t type_a, int32_t type_b, int32_t* out);
+dq_status dq_diag_mi_to_fixed(double term, uint64_t* lo, int64_t* hi);
+dq_status dq_diag_mi_from_fixed(uint64_t lo, int64_t hi, double* out);
+
 /* The grids dq_plan_consume gave the plan's last non-empty batch (host bookkeeping: no kernel, no
  * device read), so that tests can assert which kernel specialisations a plan ran and how many
  * rows each block walked.  *n_groups = the plan's scan groups (one launch each); for the first
