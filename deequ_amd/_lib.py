@@ -249,6 +249,7 @@ SIGNATURES = {
                                POINTER(c_void_p)]),
     "dq_freq_destroy": (c_int, [c_void_p]),
     "dq_freq_reset": (c_int, [c_void_p]),
+    "dq_freq_set_filter": (c_int, [c_void_p, POINTER(DqPredicate)]),
     "dq_freq_consume": (c_int, [c_void_p, POINTER(DqColumn), c_int, c_int64]),
     "dq_freq_get_summary": (c_int, [c_void_p, POINTER(DqFreqSummary)]),
     "dq_freq_size": (c_int, [c_void_p, POINTER(c_int64), POINTER(c_int64)]),

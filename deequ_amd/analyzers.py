@@ -14,6 +14,7 @@ Names, constructor arguments, preconditions, NULL -> None rules and failure metr
 from __future__ import annotations
 
 from dataclasses import dataclass, field
+from dataclasses import fields as dataclass_fields
 from typing import Callable, Dict, List, Optional
 
 from . import _lib as L
@@ -691,11 +692,40 @@ class GroupingAnalyzer(Analyzer):
         return [Preconditions.hasColumn(c) for c in self.groupingColumns()]
 
 
+def _some(where: Optional[str]) -> str:
+    return "" if where is None else ",Some(%s)" % where
+
+
+def _repr_unfiltered_as_before(self) -> str:
+    """The dataclass repr, without `where=None`: an unfiltered frequency analyzer prints as it did
+    before the field existed."""
+    parts = ["%s=%r" % (f.name, getattr(self, f.name)) for f in dataclass_fields(self)
+             if f.repr and not (f.name == "where" and self.where is None)]
+    return "%s(%s)" % (type(self).__qualname__, ", ".join(parts))
+
+
+def _filter_precondition(where: str) -> Callable[[Dict[str, str]], None]:
+    """The `where` of a frequency analyzer parses, names columns of the data (resolved as Spark 2.2
+    does, case-insensitively) and compiles for the GPU: anything else is a failure metric, as for
+    Compliance, before any data is touched."""
+    def check(schema):
+        from .predicates import compile_predicate, referenced_columns, resolve_column
+        for c in referenced_columns(where):
+            try:
+                resolve_column(c, schema)
+            except KeyError:
+                raise NoSuchColumnException("Input data does not include column %s!" % c)
+        compile_predicate(where, _engine.schema_index(schema))
+    return check
+
+
 class FrequencyBasedAnalyzer(GroupingAnalyzer):
     """FrequencyBasedAnalyzer (GroupingAnalyzers.scala:29-42): the state is the GPU group-by
-    of the grouping columns (deequ_amd.frequencies)."""
+    of the grouping columns (deequ_amd.frequencies); with `where`, of the rows where it is TRUE
+    (the state of `data.filter(where)`: numRows counts the selected rows)."""
 
     columns: tuple = ()
+    where: Optional[str] = None
 
     def __post_init__(self):
         object.__setattr__(self, "columns", _columns_tuple(self.columns))
@@ -712,14 +742,15 @@ class FrequencyBasedAnalyzer(GroupingAnalyzer):
 
     def computeStateFrom(self, data):
         from .frequencies import compute_frequencies
-        return compute_frequencies(data, self.groupingColumns())
+        return compute_frequencies(data, self.groupingColumns(), where=self.where)
 
     def preconditions(self):
         return [Preconditions.atLeastOne(self.columns)] + \
-            [Preconditions.hasColumn(c) for c in self.columns]
+            [Preconditions.hasColumn(c) for c in self.columns] + \
+            ([_filter_precondition(self.where)] if self.where is not None else [])
 
     def __str__(self):
-        return "%s(%s)" % (self.name, _scala_seq(self.columns))
+        return "%s(%s%s)" % (self.name, _scala_seq(self.columns), _some(self.where))
 
 
 class ScanShareableFrequencyBasedAnalyzer(FrequencyBasedAnalyzer):
@@ -743,7 +774,9 @@ class ScanShareableFrequencyBasedAnalyzer(FrequencyBasedAnalyzer):
 class Uniqueness(ScanShareableFrequencyBasedAnalyzer):
     """Σ[count == 1] / numRows (Uniqueness.scala:29-31)."""
     columns: tuple
+    where: Optional[str] = None
     name = "Uniqueness"
+    __repr__ = _repr_unfiltered_as_before
 
     def metric_from_summary(self, s):
         return None if s.num_groups == 0 else float(s.num_unique) / s.num_rows
@@ -755,7 +788,9 @@ class Uniqueness(ScanShareableFrequencyBasedAnalyzer):
 class Distinctness(ScanShareableFrequencyBasedAnalyzer):
     """Σ[count >= 1] / numRows (Distinctness.scala:32-34)."""
     columns: tuple
+    where: Optional[str] = None
     name = "Distinctness"
+    __repr__ = _repr_unfiltered_as_before
 
     def metric_from_summary(self, s):
         return None if s.num_groups == 0 else float(s.num_groups) / s.num_rows
@@ -767,7 +802,9 @@ class Distinctness(ScanShareableFrequencyBasedAnalyzer):
 class CountDistinct(ScanShareableFrequencyBasedAnalyzer):
     """count(*) over the frequency table (CountDistinct.scala:27-33): never NULL."""
     columns: tuple
+    where: Optional[str] = None
     name = "CountDistinct"
+    __repr__ = _repr_unfiltered_as_before
 
     def metric_from_summary(self, s):
         return float(s.num_groups)
@@ -780,7 +817,9 @@ class UniqueValueRatio(ScanShareableFrequencyBasedAnalyzer):
     """Σ[count == 1] / count(*) (UniqueValueRatio.scala:28-37).  With no groups the sum is
     NULL and the reference's `Row.getDouble` throws, which surfaces as a failure metric."""
     columns: tuple
+    where: Optional[str] = None
     name = "UniqueValueRatio"
+    __repr__ = _repr_unfiltered_as_before
 
     def metric_from_summary(self, s):
         if s.num_groups == 0:
@@ -794,7 +833,9 @@ class UniqueValueRatio(ScanShareableFrequencyBasedAnalyzer):
 class Entropy(ScanShareableFrequencyBasedAnalyzer):
     """Σ −(c/N)·ln(c/N) over the groups (Entropy.scala:31-41)."""
     column: str
+    where: Optional[str] = None
     name = "Entropy"
+    __repr__ = _repr_unfiltered_as_before
 
     def __post_init__(self):
         object.__setattr__(self, "columns", (self.column,))
@@ -803,7 +844,7 @@ class Entropy(ScanShareableFrequencyBasedAnalyzer):
         return None if s.num_groups == 0 else s.entropy
 
     def __str__(self):
-        return "Entropy(%s)" % self.column
+        return "Entropy(%s%s)" % (self.column, _some(self.where))
 
 
 # MutualInformation states of more joint groups than this are reduced on the device
@@ -823,10 +864,17 @@ class MutualInformation(FrequencyBasedAnalyzer):
     (encoded-key) order."""
     columns: tuple
     columnB: Optional[str] = field(default=None, compare=False, repr=False)  # MutualInformation(a, b)
+    where: Optional[str] = None
     name = "MutualInformation"
+    __repr__ = _repr_unfiltered_as_before
 
     def __post_init__(self):
         cols = _columns_tuple(self.columns)
+        if self.columnB is not None and len(cols) >= 2:
+            # MutualInformation([a, b], "x > 1"): the second positional argument is columnB
+            raise ValueError("MutualInformation: columns already names %d columns (%s) and a second positional "
+                             "argument %r was given, which is columnB of the form MutualInformation(a, b); pass "
+                             "a filter as where=..." % (len(cols), ", ".join(cols), self.columnB))
         if self.columnB is not None:
             cols = cols + (self.columnB,)
             object.__setattr__(self, "columnB", None)
@@ -867,7 +915,7 @@ class MutualInformation(FrequencyBasedAnalyzer):
         return metric_from_value(value, self.name, self.instance(), self.entity)
 
     def __str__(self):
-        return "MutualInformation(%s)" % _scala_seq(self.columns)
+        return "MutualInformation(%s%s)" % (_scala_seq(self.columns), _some(self.where))
 
 
 MAXIMUM_ALLOWED_DETAIL_BINS = 1000  # Histogram.MaximumAllowedDetailBins (Histogram.scala:109)
@@ -1045,4 +1093,19 @@ def _memoise_hashes() -> None:
                 sub.__hash__ = caching(h)
 
 
+def _unfiltered_hashes_as_before() -> None:
+    """`where` joined the frequency analyzers' fields later: with where=None their hash stays the
+    hash of the fields they had (the generated __hash__ would mix a None in)."""
+    def keeping(full, names):
+        def __hash__(self):
+            if self.where is None:
+                return hash(tuple(getattr(self, n) for n in names))
+            return full(self)
+        return __hash__
+    for cls in (Uniqueness, Distinctness, CountDistinct, UniqueValueRatio, Entropy, MutualInformation):
+        names = [f.name for f in dataclass_fields(cls) if f.compare and f.name != "where"]
+        cls.__hash__ = keeping(cls.__dict__["__hash__"], names)
+
+
+_unfiltered_hashes_as_before()
 _memoise_hashes()

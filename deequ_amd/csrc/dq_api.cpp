@@ -645,6 +645,55 @@ static dq_status validate_predicate(const dq_predicate& p, const int32_t* types,
   return DQ_OK;
 }
 
+// The device tables of a set of validated programs, as launch_predicates and launch_match_mask
+// read them (a plan's programs, a frequency table's filter): the instructions back to back, string
+// literals as offsets into one pool, and one match task per distinct (column, pattern, mode) of the
+// LIKE / RLIKE instructions, the distinct patterns' images back to back in `images` (which may
+// already hold other images: PatternMatch's).
+struct ProgramTables {
+  std::vector<PredInsn> insns;
+  std::string pool;
+  bool cast = false;  // a program casts a string to double (the interpreter's CAST kernel)
+  std::vector<MatchTask>& tasks;
+  std::vector<std::string>& keys;      // of the distinct patterns
+  std::vector<uint32_t>& offsets;      // of each key's image in `images`
+  std::vector<uint8_t>& images;
+  uint32_t& lds;                       // bytes of the largest staged image
+  // Appends one program; returns where it lies in `insns`.
+  PredProgram add(const Program& p) {
+    const PredProgram at{(int32_t)insns.size(), (int32_t)p.code.size()};
+    for (PredInsn in : p.code) {
+      if (in.opcode == DQ_P_LIT_STRING) in.i64 += (int64_t)pool.size();  // offset into the shared pool
+      if (in.opcode == DQ_P_CAST_DOUBLE) cast = true;
+      if (in.opcode == kPredMatch) {  // the task for this (column, pattern, mode)
+        const ProgramMatch& m = p.matches[(size_t)in.i64];
+        int d = -1;
+        for (size_t k = 0; k < keys.size(); ++k)
+          if (keys[k] == m.key) d = (int)k;
+        if (d < 0) {
+          d = (int)keys.size();
+          keys.push_back(m.key);
+          offsets.push_back((uint32_t)images.size());
+          images.insert(images.end(), m.image->begin(), m.image->end());
+          lds = std::max(lds, (uint32_t)m.image->size() - regex::kRegexHeaderBytes);
+        }
+        const uint32_t off = offsets[d];
+        int t = -1;
+        for (size_t k = 0; k < tasks.size(); ++k)
+          if (tasks[k].column == m.column && tasks[k].dfa_off == off) t = (int)k;
+        if (t < 0) {
+          tasks.push_back(MatchTask{m.column, off});
+          t = (int)tasks.size() - 1;
+        }
+        in.i64 = t;
+      }
+      insns.push_back(in);
+    }
+    pool += p.pool;
+    return at;
+  }
+};
+
 static int cmp_of(int opcode) {
   switch (opcode) {
     case DQ_P_EQ: return CMP_EQ;
@@ -1308,40 +1357,12 @@ extern "C" dq_status dq_plan_create(dq_ctx* ctx, const dq_op* ops, int n_ops,
     return DQ_OK;
   };
   std::vector<PredProgram> progs;
-  std::vector<PredInsn> insns;
-  std::string pool;
-  plan->pred_cast = false;
-  for (const auto& p : plan->programs) {
-    progs.push_back(PredProgram{(int32_t)insns.size(), (int32_t)p.code.size()});
-    for (PredInsn in : p.code) {
-      if (in.opcode == DQ_P_LIT_STRING) in.i64 += (int64_t)pool.size();  // plan-wide pool offset
-      if (in.opcode == DQ_P_CAST_DOUBLE) plan->pred_cast = true;
-      if (in.opcode == kPredMatch) {  // the plan's task for this (column, pattern, mode)
-        const ProgramMatch& m = p.matches[(size_t)in.i64];
-        int d = -1;
-        for (size_t k = 0; k < plan->match_keys.size(); ++k)
-          if (plan->match_keys[k] == m.key) d = (int)k;
-        if (d < 0) {
-          d = (int)plan->match_keys.size();
-          plan->match_keys.push_back(m.key);
-          plan->match_offsets.push_back((uint32_t)plan->regex_images.size());
-          plan->regex_images.insert(plan->regex_images.end(), m.image->begin(), m.image->end());
-          plan->match_lds = std::max(plan->match_lds, (uint32_t)m.image->size() - regex::kRegexHeaderBytes);
-        }
-        const uint32_t off = plan->match_offsets[d];
-        int t = -1;
-        for (size_t k = 0; k < plan->match_tasks.size(); ++k)
-          if (plan->match_tasks[k].column == m.column && plan->match_tasks[k].dfa_off == off) t = (int)k;
-        if (t < 0) {
-          plan->match_tasks.push_back(MatchTask{m.column, off});
-          t = (int)plan->match_tasks.size() - 1;
-        }
-        in.i64 = t;
-      }
-      insns.push_back(in);
-    }
-    pool += p.pool;
-  }
+  ProgramTables tables{{}, {}, false, plan->match_tasks, plan->match_keys, plan->match_offsets, plan->regex_images,
+                       plan->match_lds};
+  for (const auto& p : plan->programs) progs.push_back(tables.add(p));
+  plan->pred_cast = tables.cast;
+  std::vector<PredInsn>& insns = tables.insns;
+  std::string& pool = tables.pool;
   pool.append(8, '\0');
   // HLL and DataType of the same utf8 (column, where) -- every string column of the profiler's
   // pass 1 -- run as one string pass (one read of the strings); the rest keep their own kernels

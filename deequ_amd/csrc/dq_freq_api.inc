@@ -9,7 +9,7 @@
 
 enum FreqCounter {
   FC_GROUPS = 0, FC_HEAP_USED, FC_OVERFLOW, FC_NEED, FC_NBIG, FC_EXPORT_N, FC_STAGED, FC_RETRY, FC_MAXLEN,
-  FC_PART_OVF, FC_PART_FLAG, FC_IMP_RECS, FC_PACK_PROBE, FC_UUID_BAD, FC_UUID_GOOD, FC_PROBE_LONG, FC_COUNT
+  FC_PART_OVF, FC_PART_FLAG, FC_IMP_RECS, FC_PACK_PROBE, FC_UUID_BAD, FC_UUID_GOOD, FC_PROBE_LONG, FC_SELECTED, FC_COUNT
 };
 
 // Distinct-key estimate of the staging sketch, used only to size the table.  This is the plain
@@ -129,6 +129,18 @@ struct dq_freq : Stager {
   bool few_only = false;                // DQ_FREQ_FEW_ONLY: the few-groups kernel or DQ_ERR_SPACE
   bool few_failed = false;              // a DQ_FREQ_FEW_ONLY batch did not fit: every consume fails
   std::vector<DevColumn> h_cols;
+  // The table's `where` (dq_freq_set_filter): one validated program, uploaded once.  Every batch
+  // evaluates it into d_fwords {TRUE words, NOT NULL words} (LIKE / RLIKE: match masks first, into
+  // d_fmatch_words) and folds the TRUE words into the first key column's validity (d_fvalid), so
+  // every path below sees a filtered-out row as a NULL key.  The selected rows are counted on the
+  // device (FC_SELECTED, a running total); read_counters settles it into num_rows, in the read
+  // every path makes after staging: rows_pending says that a batch is not settled yet.
+  bool filtered = false, filter_cast = false, rows_pending = false;
+  uint32_t filter_lds = 0;
+  int filter_matches = 0;
+  unsigned long long rows_settled = 0;  // of FC_SELECTED, already in num_rows
+  std::vector<DevColumn> filter_cols;
+  DevBuf d_fprog, d_finsns, d_fpool, d_fmatch, d_fdfas, d_fcols, d_fwords, d_fmatch_words, d_fvalid;
 
   ~dq_freq() {
     if (stream) StreamPool::get().release(ctx ? ctx->device : 0, stream);
@@ -161,8 +173,20 @@ struct dq_freq : Stager {
     DQ_HIP(hipMemcpyAsync(h_ctr, d_ctr.ptr, FC_COUNT * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
     DQ_HIP(hipStreamSynchronize(stream));
     std::memcpy(h, h_ctr, FC_COUNT * sizeof(unsigned long long));
+    if (filtered) {  // the selected rows of the batches consumed since the last read
+      num_rows += (int64_t)(h[FC_SELECTED] - rows_settled);
+      rows_settled = h[FC_SELECTED];
+      rows_pending = false;
+    }
     return DQ_OK;
   }
+  // num_rows is current: a filtered table's last batches may be counted on the device only.
+  dq_status settle_rows() {
+    if (!rows_pending) return DQ_OK;
+    unsigned long long h[FC_COUNT];
+    return read_counters(h);
+  }
+  dq_status apply_filter(int n_columns, int64_t n_rows);
 
   // Grow to keep (groups + incoming) below a 0.6 load factor (per-slice loads scatter around
   // the mean: at 0.6 a 2048-slot slice is 5 sigma away from full).
@@ -1279,6 +1303,8 @@ extern "C" dq_status dq_freq_reset(dq_freq* f) {
   DQ_HIP(hipMemsetAsync(f->d_sketch.ptr, 0, kHllM * sizeof(uint32_t), f->stream));
   DQ_HIP(hipStreamSynchronize(f->stream));
   f->num_rows = 0;
+  f->rows_settled = 0;  // (FC_SELECTED was cleared with the counters; the filter itself stays)
+  f->rows_pending = false;
   f->staged = 0;
   f->compact = false;
   f->table_cleared = true;
@@ -1296,6 +1322,86 @@ extern "C" dq_status dq_freq_reset(dq_freq* f) {
   f->d_part1.release();
   f->d_rows.release();
   f->d_povf.release();
+  return DQ_OK;
+}
+
+extern "C" dq_status dq_freq_set_filter(dq_freq* f, const dq_predicate* where) {
+  if (!f || !where) return fail(DQ_ERR_INVALID, "NULL argument");
+  if (f->ks.null_as_key)
+    return fail(DQ_ERR_UNSUPPORTED, "DQ_FREQ_NULL_AS_KEY: a Histogram table groups its invalid rows, so a row the "
+                                    "filter drops cannot be told from a NULL key by validity (no filter on such a table)");
+  Program prog;
+  DQ_TRY(validate_predicate(*where, f->col_types.data(), (int)f->col_types.size(), &prog));
+  DQ_HIP(hipSetDevice(f->ctx->device));
+  unsigned long long h[FC_COUNT];
+  DQ_TRY(f->read_counters(h));
+  if (f->num_rows != 0 || f->staged != 0 || h[FC_GROUPS] != 0 || h[FC_SELECTED] != 0)
+    return fail(DQ_ERR_STATE, "dq_freq_set_filter: the table already holds rows or groups (a filter is set on an empty table)");
+  // the program's tables, laid out as a plan's (ProgramTables): one program, its pool, one match
+  // task per LIKE / RLIKE
+  std::vector<MatchTask> tasks;
+  std::vector<std::string> keys;
+  std::vector<uint32_t> offsets;
+  std::vector<uint8_t> images;
+  uint32_t lds = 0;
+  ProgramTables tables{{}, {}, false, tasks, keys, offsets, images, lds};
+  const PredProgram pp = tables.add(prog);
+  const std::vector<PredInsn>& insns = tables.insns;
+  std::string pool = tables.pool;
+  pool.append(8, '\0');
+  const bool cast = tables.cast;
+  auto upload = [&](DevBuf& buf, const void* src, size_t bytes) -> dq_status {
+    if (bytes == 0) return DQ_OK;
+    DQ_TRY(buf.ensure(bytes));
+    DQ_HIP(hipMemcpy(buf.ptr, src, bytes, hipMemcpyHostToDevice));
+    return DQ_OK;
+  };
+  DQ_TRY(upload(f->d_fprog, &pp, sizeof(pp)));
+  DQ_TRY(upload(f->d_finsns, insns.data(), insns.size() * sizeof(PredInsn)));
+  DQ_TRY(upload(f->d_fpool, pool.data(), pool.size()));
+  DQ_TRY(upload(f->d_fmatch, tasks.data(), tasks.size() * sizeof(MatchTask)));
+  DQ_TRY(upload(f->d_fdfas, images.data(), images.size()));
+  DQ_TRY(f->d_fcols.ensure(f->col_types.size() * sizeof(DevColumn)));
+  for (int c : prog.columns) f->col_used[c] = true;
+  f->filter_matches = (int)tasks.size();
+  f->filter_lds = lds;
+  f->filter_cast = cast;
+  f->filtered = true;
+  return DQ_OK;
+}
+
+// The filter over the prepared batch (h_cols): evaluate, fold into the first key column's validity,
+// count the selected rows on the device; h_cols[first key].validity then names the folded bitmap.
+dq_status dq_freq::apply_filter(int n_columns, int64_t n_rows) {
+  const int64_t wpm = ((n_rows + 63) >> 6) + 1;
+  const size_t words = (size_t)wpm * sizeof(uint64_t);
+  // Every path of dq_freq_consume reads the counters after its last kernel that reads the folded
+  // bitmap, so the stream is idle here and the buffers may be regrown.  rows_pending still set means
+  // that the previous consume failed midway: its kernels may be running, so the stream drains
+  // before an old block goes back to the pool.
+  if (rows_pending && (d_fwords.cap < 2 * words || d_fvalid.cap < words || d_fmatch_words.cap < words * filter_matches))
+    DQ_HIP(hipStreamSynchronize(stream));
+  DQ_TRY(d_fwords.ensure(2 * words));
+  DQ_TRY(d_fvalid.ensure(words));
+  // (the descriptors the filter reads, before the fold: its own copies on both sides, the paths
+  // below rewrite h_cols and d_cols)
+  filter_cols = h_cols;
+  DQ_HIP(hipMemcpyAsync(d_fcols.ptr, filter_cols.data(), n_columns * sizeof(DevColumn), hipMemcpyHostToDevice, stream));
+  const DevColumn* dcols = static_cast<const DevColumn*>(d_fcols.ptr);
+  if (filter_matches > 0) {
+    DQ_TRY(d_fmatch_words.ensure((size_t)wpm * filter_matches * sizeof(uint64_t)));
+    DQ_HIP(launch_match_mask(static_cast<const MatchTask*>(d_fmatch.ptr), filter_matches, dcols,
+                             static_cast<const uint8_t*>(d_fdfas.ptr), filter_lds, n_rows,
+                             static_cast<uint64_t*>(d_fmatch_words.ptr), wpm, stream));
+  }
+  DQ_HIP(launch_predicates(static_cast<const PredProgram*>(d_fprog.ptr), 1, static_cast<const PredInsn*>(d_finsns.ptr),
+                           static_cast<const uint8_t*>(d_fpool.ptr), dcols, n_rows, static_cast<uint64_t*>(d_fwords.ptr),
+                           wpm, filter_cast, stream, static_cast<const uint64_t*>(d_fmatch_words.ptr)));
+  DevColumn& key = h_cols[ks.key_cols[0]];
+  DQ_HIP(launch_freq_filter(static_cast<const uint64_t*>(d_fwords.ptr), key.validity, n_rows,
+                            static_cast<uint64_t*>(d_fvalid.ptr), ctr() + FC_SELECTED, stream));
+  key.validity = static_cast<const uint8_t*>(d_fvalid.ptr);
+  rows_pending = true;
   return DQ_OK;
 }
 
@@ -1320,7 +1426,9 @@ extern "C" dq_status dq_freq_consume(dq_freq* f, const dq_column* columns, int n
     std::memset(&f->h_cols[c], 0, sizeof(DevColumn));
     if (f->col_used[c]) DQ_TRY(prepare_column(f, c, columns[c], n_rows, &f->h_cols[c]));
   }
-  f->num_rows += n_rows;
+  const int64_t rows_before = f->num_rows;
+  if (f->filtered) DQ_TRY(f->apply_filter(n_columns, n_rows));  // (counts the selected rows itself)
+  else f->num_rows += n_rows;
   if (f->sorted_path && f->part_path &&
       std::max<uint64_t>((uint64_t)n_rows, f->reserve_rows) >= f->part_min) {
     // large stagings: records go straight into their level-1 regions (partition path)
@@ -1398,7 +1506,8 @@ extern "C" dq_status dq_freq_consume(dq_freq* f, const dq_column* columns, int n
   }
   if (f->few_only) {  // (nothing of this batch was merged)
     f->few_failed = true;
-    f->num_rows -= n_rows;
+    DQ_TRY(f->settle_rows());
+    f->num_rows = rows_before;
     return fail(DQ_ERR_SPACE, "DQ_FREQ_FEW_ONLY: the column has more groups than the few-groups path holds");
   }
   if (f->few_groups > 0 && n_rows > f->sub_rows) {
@@ -1556,6 +1665,7 @@ extern "C" dq_status dq_freq_get_summary(dq_freq* f, dq_freq_summary* out) {
   DQ_HIP(hipSetDevice(f->ctx->device));
   std::vector<unsigned long long> hist, big;
   DQ_TRY(freq_hist(f, hist, big));
+  DQ_TRY(f->settle_rows());
   summary_from_hist(hist, big, f->num_rows, out);
   return DQ_OK;
 }

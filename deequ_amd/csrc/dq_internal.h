@@ -588,6 +588,14 @@ hipError_t launch_predicates(const PredProgram* d_progs, int n_progs, const Pred
 hipError_t launch_match_mask(const MatchTask* d_tasks, int n_tasks, const DevColumn* d_cols, const uint8_t* d_dfas,
                              uint32_t lds_bytes, int64_t n_rows, uint64_t* d_out, int64_t words_per_mask,
                              hipStream_t stream);
+// A filtered frequency table's batch (dq_freq_set_filter, dq_pred.hip: dq_freq_filter_kernel): the
+// filter's TRUE words folded into the first key column's validity.  d_out (8-byte aligned, room for
+// (n_rows + 63) / 64 + 1 words) gets TRUE & validity as an Arrow bitmap at bit 0, every bit at and
+// past n_rows 0 (validity: that column's bitmap at bit 0, any byte alignment, (n_rows + 7) / 8
+// bytes; nullptr = all valid); *d_selected += the TRUE bits.  Same geometry as launch_predicates.
+constexpr int64_t kFreqFilterMaxBlocks = 2048;
+hipError_t launch_freq_filter(const uint64_t* d_true_words, const uint8_t* validity, int64_t n_rows, uint64_t* d_out,
+                              unsigned long long* d_selected, hipStream_t stream);
 hipError_t launch_rebase_offsets(int32_t* d_offs, int64_t n, int32_t first, hipStream_t stream);
 hipError_t launch_realign_bitmap(const uint8_t* src, int64_t bit_offset, int64_t n_bits,
                                  uint8_t* dst, hipStream_t stream);

@@ -78,6 +78,63 @@ hipError_t launch_predicates(const PredProgram* d_progs, int n_progs, const Pred
   return hipGetLastError();
 }
 
+// The `where` of a frequency table (dq_freq_set_filter): a row takes part only where the filter is
+// TRUE, and every frequency stage drops a row by the key columns' validity alone, so the filter's
+// TRUE word is folded into the first key column's validity: out word w = TRUE word w & validity
+// bits [64 w, 64 w + 64).  One wave per word, as dq_pred_kernel: lanes 0..7 load the word's
+// validity bytes (the bitmap may start at any byte and end with the batch's last byte), lane 0
+// stores the word.  The TRUE words are 0 at and past n_rows, so the bitmap is too; the word after
+// the last is zeroed for readers of whole dwords.  *selected += the TRUE bits (numRows of the
+// filtered data): one atomic per workgroup, an integer sum in any order.
+__global__ __launch_bounds__(kBlock) void dq_freq_filter_kernel(const uint64_t* __restrict__ true_words,
+                                                                const uint8_t* __restrict__ validity, int64_t n_rows,
+                                                                uint64_t* __restrict__ out,
+                                                                unsigned long long* selected) {
+  __shared__ unsigned long long s_sel[kBlock / 64];
+  const uint32_t lane = threadIdx.x & 63u;
+  const int64_t n_words = (n_rows + 63) >> 6;
+  const int64_t n_bytes = (n_rows + 7) >> 3;
+  unsigned long long sel = 0;
+  for (int64_t w = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); w < n_words;
+       w += (int64_t)gridDim.x * (kBlock / 64)) {
+    const uint64_t t = true_words[w];
+    uint64_t v = ~0ull;
+    if (validity != nullptr) {
+      const int64_t b = (w << 3) + lane;
+      const uint32_t byte = (lane < 8u && b < n_bytes) ? validity[b] : 0u;
+      uint32_t lo = 0u, hi = 0u;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        lo |= (uint32_t)__builtin_amdgcn_readlane((int)byte, k) << (8 * k);
+        hi |= (uint32_t)__builtin_amdgcn_readlane((int)byte, 4 + k) << (8 * k);
+      }
+      v = ((uint64_t)hi << 32) | lo;
+    }
+    if (lane == 0u) {
+      out[w] = t & v;
+      if (w == n_words - 1) out[n_words] = 0ull;
+    }
+    sel += (unsigned long long)__popcll(t);
+  }
+  if (lane == 0u) s_sel[threadIdx.x >> 6] = sel;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long sum = 0;
+    for (int k = 0; k < kBlock / 64; ++k) sum += s_sel[k];
+    if (sum) atomicAdd(selected, sum);
+  }
+}
+
+hipError_t launch_freq_filter(const uint64_t* d_true_words, const uint8_t* validity, int64_t n_rows, uint64_t* d_out,
+                              unsigned long long* d_selected, hipStream_t stream) {
+  if (n_rows <= 0) return hipSuccess;
+  const int64_t n_words = (n_rows + 63) >> 6;
+  const int64_t blocks = std::min<int64_t>((n_words + 3) / 4, kFreqFilterMaxBlocks);
+  hipLaunchKernelGGL(dq_freq_filter_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, stream, d_true_words, validity,
+                     n_rows, d_out, d_selected);
+  return hipGetLastError();
+}
+
 // offs[i] -= first: utf8 offsets of a host batch copied verbatim, rebased to its first byte
 __global__ void dq_rebase_offsets_kernel(int32_t* __restrict__ offs, int64_t n, int32_t first) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)

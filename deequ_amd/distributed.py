@@ -461,8 +461,10 @@ class _DistributedTableView:
 
 
 def compute_frequencies_distributed(data, grouping_columns, histogram: bool = False, group=None,
-                                    table_factory=None):
-    """FrequencyBasedAnalyzer.computeFrequencies over the union of every rank's shard `data`."""
+                                    table_factory=None, where=None):
+    """FrequencyBasedAnalyzer.computeFrequencies over the union of every rank's shard `data`; with
+    `where`, every rank filters its own shard before the exchange and numRows is the sum of the
+    ranks' selected rows."""
     import torch
     import torch.distributed as dist
     from .frequencies import FrequencyTable
@@ -470,7 +472,8 @@ def compute_frequencies_distributed(data, grouping_columns, histogram: bool = Fa
     schema = data.schema
     local, n_local, err = None, 0, None
     try:
-        local = make(grouping_columns, {c: schema[c] for c in schema}, histogram)
+        local = make(grouping_columns, {c: schema[c] for c in schema}, histogram,
+                     **({} if where is None else {"where": where}))
         for batch in data.batches():
             local.consume(batch)
         n_local = local.summary().num_rows

@@ -85,10 +85,14 @@ class FrequencyTable:
     `schema` is the batch schema handed to `consume` (defaults to the key columns alone);
     `histogram=True` is Histogram's NULL-as-"NullValue" grouping (DQ_FREQ_NULL_AS_KEY);
     `few_only=True` groups with the few-groups kernel alone (DQ_FREQ_FEW_ONLY): a batch with more
-    distinct keys than it holds raises DeequAmdError with status DQ_ERR_SPACE."""
+    distinct keys than it holds raises DeequAmdError with status DQ_ERR_SPACE;
+    `where` is a SQL filter over the batch schema in the language of deequ_amd.predicates
+    (dq_freq_set_filter): the table holds the state of `data.filter(where)` -- a row takes part
+    only where the filter is TRUE, and numRows counts the selected rows.  What the predicate
+    compiler declines raises UnsupportedPredicate; a Histogram table takes no filter."""
 
     def __init__(self, key_columns: Sequence[str], schema: Dict[str, str], histogram: bool = False,
-                 device: Optional[int] = None, few_only: bool = False):
+                 device: Optional[int] = None, few_only: bool = False, where: Optional[str] = None):
         from .decimals import reject_decimal
         from .engine import current_device
         reject_decimal(schema, key_columns, "Histogram" if histogram else "frequency group-by")
@@ -106,10 +110,25 @@ class FrequencyTable:
         L.check(L.lib().dq_freq_create(ctx.handle, idx, len(self.key_columns), types, len(self.names), flags,
                                        ctypes.byref(h)))
         self.handle = h
+        self.where = where
+        if where is not None:
+            from .engine import _fill_pred, _pred_array, schema_index
+            from .predicates import compile_predicate
+            packed = _pred_array(compile_predicate(where, schema_index(self.schema)))
+            pred = L.DqPredicate()
+            _fill_pred(pred, packed)
+            L.check(L.lib().dq_freq_set_filter(self.handle, ctypes.byref(pred)))
+
+    def reset(self) -> None:
+        """Empty the table (dq_freq_reset); its filter stays."""
+        L.check(L.lib().dq_freq_reset(self.handle))
 
     @classmethod
     def like(cls, other: "FrequencyTable") -> "FrequencyTable":
-        """An empty table with the same key columns (and a key-only schema)."""
+        """An empty table with the same key columns and the same filter (a key-only schema; with a
+        filter the whole batch schema, which the filter is compiled against)."""
+        if other.where is not None:
+            return cls(other.key_columns, other.schema, other.histogram, other.device, where=other.where)
         return cls(other.key_columns, {c: t for c, t in zip(other.key_columns, other.dtypes)},
                    other.histogram, other.device)
 
@@ -350,14 +369,16 @@ def _unpack_groups(groups, n: int, raw: bytes) -> Tuple[np.ndarray, List[bytes]]
     return g["count"].copy(), [raw[o:o + m] for o, m in zip(offs, lens)]
 
 
-def compute_frequencies(data, grouping_columns: Sequence[str], histogram: bool = False) -> "FrequenciesAndNumRows":
-    """FrequencyBasedAnalyzer.computeFrequencies over every batch of `data` (one pass); over a
-    ShardedTable, the key-hash exchanged table of the whole dataset (collective)."""
+def compute_frequencies(data, grouping_columns: Sequence[str], histogram: bool = False,
+                        where: Optional[str] = None) -> "FrequenciesAndNumRows":
+    """FrequencyBasedAnalyzer.computeFrequencies over every batch of `data` (one pass), with
+    `where` over the rows it selects; over a ShardedTable, the key-hash exchanged table of the
+    whole dataset (collective: every rank filters its own shard first)."""
     from .distributed import compute_frequencies_distributed, is_sharded
     if is_sharded(data):
-        return compute_frequencies_distributed(data.local, grouping_columns, histogram, group=data.group)
+        return compute_frequencies_distributed(data.local, grouping_columns, histogram, group=data.group, where=where)
     schema = data.schema
-    table = FrequencyTable(grouping_columns, {c: schema[c] for c in schema}, histogram)
+    table = FrequencyTable(grouping_columns, {c: schema[c] for c in schema}, histogram, where=where)
     table.reserve(data.count())
     for batch in data.batches():
         table.consume(batch)

@@ -82,6 +82,12 @@ def _distinct(analyzers: Iterable[Analyzer]) -> List[Analyzer]:
     return out
 
 
+def grouping_key(analyzer) -> tuple:
+    """What the grouping analyzers that share one frequency table agree on: (sorted grouping
+    columns, where).  A different filter is a different table and a different persisted state."""
+    return tuple(sorted(analyzer.groupingColumns())), getattr(analyzer, "where", None)
+
+
 class AnalysisRunner:
     @staticmethod
     def onData(data) -> "AnalysisRunBuilder":
@@ -112,17 +118,17 @@ class AnalysisRunner:
 
     @staticmethod
     def _runGroupingAnalyzers(data, analyzers, aggregateWith, saveStatesWith, states_out=None) -> AnalyzerContext:
-        """One GPU group-by per sorted grouping-column set (AnalysisRunner.scala:172-186,
+        """One GPU group-by per (sorted grouping-column set, where) (AnalysisRunner.scala:172-186,
         259-287), metrics of all analyzers of that grouping from the one table (:480-548)."""
         from .frequencies import compute_frequencies
         from .states import merge
         groups = OrderedDict()
         for a in analyzers:
-            groups.setdefault(tuple(sorted(a.groupingColumns())), []).append(a)
+            groups.setdefault(grouping_key(a), []).append(a)
         results = OrderedDict()
-        for cols, group in groups.items():
+        for (cols, where), group in groups.items():
             try:
-                state = compute_frequencies(data, list(cols))
+                state = compute_frequencies(data, list(cols), where=where)
                 if aggregateWith is not None:
                     state = merge(state, aggregateWith.load(group[0]))
             except Exception as e:  # noqa: BLE001 - the group-by itself failed
@@ -136,7 +142,7 @@ class AnalysisRunner:
                     results[a] = a.toFailureMetric(e)
             if saveStatesWith is not None:
                 saveStatesWith.persist(group[0], state)
-            if states_out is not None:
+            if states_out is not None and where is None:  # (a Histogram shares an unfiltered table only)
                 states_out[cols] = state
         return AnalyzerContext(results)
 
@@ -265,7 +271,7 @@ class AnalysisRunner:
         """Metrics from the merge of persisted states, no data scan (AnalysisRunner.scala:385-460):
         every analyzer's states are summed over the loaders (aggregateStateTo, Analyzer.scala:
         130-147); scanning analyzers compute their metric from that; grouping analyzers of one
-        grouping-column set share the one frequency state any of them has (only the first of a
+        grouping-column set and filter share the one frequency state any of them has (only the first of a
         set is persisted, :543; findStateForParticularGrouping, :462-476)."""
         from .analyzers import GroupingAnalyzer
         from .states import merge
@@ -294,7 +300,7 @@ class AnalysisRunner:
             if a in results:
                 continue
             if isinstance(a, GroupingAnalyzer):
-                grouping.setdefault(tuple(sorted(a.groupingColumns())), []).append(a)
+                grouping.setdefault(grouping_key(a), []).append(a)
                 continue
             try:
                 state = aggregated.get(a)

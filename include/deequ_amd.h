@@ -452,7 +452,9 @@ dq_status dq_profile_few_strings(dq_ctx* ctx, int32_t n, const dq_column* cols, 
  * group-by of Histogram (Histogram.scala:54-69).  A dq_freq is the device-resident state
  * FrequenciesAndNumRows(frequencies, numRows) (GroupingAnalyzers.scala:124-157): consuming a
  * batch groups its rows (rows with a NULL grouping value are dropped, numRows counts every
- * row); importing groups is FrequenciesAndNumRows.sum (outer join adding counts).
+ * row); importing groups is FrequenciesAndNumRows.sum (outer join adding counts).  With a filter
+ * (dq_freq_set_filter) the state is that of the filtered data: only rows where the filter is TRUE
+ * take part, and numRows counts every selected row (a selected row with a NULL key too).
  *
  * Group keys are exchanged in an encoded form: fixed-width columns as little-endian value bytes
  * (1 B bool/int8, 2 B int16, 4 B int32/float32, 8 B int64/float64; floats as raw bits), strings
@@ -496,6 +498,17 @@ dq_status dq_freq_reserve(dq_freq* f, int64_t rows);
  * is aggregated in LDS per workgroup instead of being staged and sorted. */
 dq_status dq_freq_expect_groups(dq_freq* f, int64_t groups);
 dq_status dq_freq_reset(dq_freq* f);
+/* The table's `where`: every later batch is grouped as data.filter(where) would be (SQL WHERE: a
+ * FALSE or NULL verdict drops the row).  The program's column indices are batch column indices,
+ * like key_columns; it is validated as a plan validates a `where` (what a plan declines is
+ * declined here with the same status and message).  Set on an empty table (DQ_ERR_STATE once it
+ * holds rows or groups); dq_freq_reset keeps it.  DQ_ERR_UNSUPPORTED on a DQ_FREQ_NULL_AS_KEY
+ * table.  Per batch the evaluation adds one descriptor copy and two small launches (the predicate
+ * mask and its fold into the first key column's validity; three with a LIKE / RLIKE, whose match
+ * masks come first) on the table's stream, and no host synchronisation of its own: the selected
+ * rows are counted on the device and read back with the counters every path reads anyway.  A
+ * table without a filter runs exactly what it ran before. */
+dq_status dq_freq_set_filter(dq_freq* f, const dq_predicate* where);
 dq_status dq_freq_consume(dq_freq* f, const dq_column* columns, int n_columns, int64_t n_rows);
 /* dq_freq_consume of one Arrow batch (dq_plan_consume_arrow's rules; all the batch's columns). */
 dq_status dq_freq_consume_arrow(dq_freq* f, const struct ArrowSchema* schema, const struct ArrowArray* array,
