@@ -2436,7 +2436,11 @@ struct StageStrings {
   uint32_t pob[kStagePer], poe[kStagePer], vword;
   uint32_t kw[kStagePer][4], lens[(kStagePer + 3) / 4], sel;
 
-  // False (the workgroup returns): a heap under 16 bytes -- key_load16's general path, as a long key.
+  // False (the workgroup returns): a heap under 16 bytes, which key_load16 cannot read -- the batch goes
+  // to the general path.  It is reported as a key longer than any record format holds (kMaxLocalKey +
+  // 1), not as a 16-byte key: the host rolls the batch back either way, but a key of 16 to
+  // kMaxLocalKey bytes also turns the table to hashed records for good, and a batch of one short
+  // key must not do that.
   __device__ __forceinline__ bool open(const DevColumn& c, int64_t n, int32_t nulls, unsigned long long* long_key) {
     offsets = uniform_ptr(c.offsets);
     n_rows = n;
@@ -2445,7 +2449,7 @@ struct StageStrings {
     const uint8_t* vals = static_cast<const uint8_t*>(uniform_ptr(c.values));
     rs_vals = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(vals), 0, (int)heap_end, 0x00020000);
     if (heap_end < 16u) {
-      if (blockIdx.x == 0 && threadIdx.x == 0) atomicMax(long_key, 16ull);
+      if (blockIdx.x == 0 && threadIdx.x == 0) atomicMax(long_key, (unsigned long long)kMaxLocalKey + 1ull);
       return false;
     }
     validity = uniform_ptr(c.validity);
@@ -4487,7 +4491,7 @@ hipError_t launch_freq_part(const void* d_in, uint64_t in_n, const unsigned long
   return hipGetLastError();
 }
 
-// Whether a single-utf8-key staging should pack its keys (dq_keypack.h): a strided sample of
+// Whether a single-utf8-key staging should pack its keys (dq_keypack.h): a scattered sample of
 // the batch's rows (kPackProbe of them) is checked, and out[0] counts the sampled non-NULL keys
 // that do not pack (longer than 15 bytes or not a digit string).  A batch whose keys mostly do
 // not pack would fill the packed stage's overflow list and be staged twice.

@@ -104,6 +104,8 @@ struct dq_freq : Stager {
   uint64_t diag_part_runs = 0, diag_sort_records = 0, diag_packed_runs = 0;
   uint64_t diag_import_coarse = 0, diag_import_skipped = 0;  // wire runs cut at coarser slices / inserted one by one
   int diag_part_bits = 0;
+  // batches rolled back out of the regions / regions aggregated because a batch of another record format arrived
+  uint64_t diag_rollbacks = 0, diag_materialized_for_format = 0;
   // derived views, valid until the table changes (consume / import / merge / reset)
   bool hist_valid = false;
   std::vector<unsigned long long> hist_cache, big_cache;  // count-of-counts (freq_hist)
@@ -270,6 +272,15 @@ struct dq_freq : Stager {
   dq_status materialize() {
     DQ_TRY(aggregate());
     return expand();
+  }
+  // materialize() for an operation that is about to change the table.  The derived views are
+  // dropped after it, not before: its own aggregation, when it runs on the partition path into an
+  // empty table, marks the count-of-counts and the slice maxima valid, and they would then
+  // describe the table as it was before the operation's rows.
+  dq_status materialize_for_write() {
+    DQ_TRY(materialize());
+    invalidate();
+    return DQ_OK;
   }
 
   // Aggregate the staged records into the table: group them by slice (bucket split), one work item per slice's bucket
@@ -493,7 +504,10 @@ struct dq_freq : Stager {
   // kernel: no host round trip before the launch; a rolled-back batch's hashes must not inflate
   // the table's size) and the batch's longest-key counter is cleared.
   dq_status begin_region_stage(int64_t n_rows, bool compatible) {
-    if (staged > 0 && !(region_staged && compatible)) DQ_TRY(materialize());
+    if (staged > 0 && !(region_staged && compatible)) {
+      if (region_staged) ++diag_materialized_for_format;  // (else a contiguous staging: no format to change)
+      DQ_TRY(materialize());
+    }
     if (region_rows == 0 || staged + (uint64_t)n_rows > region_rows) {
       if (staged > 0) DQ_TRY(materialize());
       DQ_TRY(alloc_regions(std::max<uint64_t>((uint64_t)n_rows, reserve_rows)));
@@ -513,6 +527,7 @@ struct dq_freq : Stager {
   // them, the overflow flag cleared, the staged count as it was, and the heap cursor back at
   // *heap_used (the hashed stage; nullptr: the heap was not written).
   dq_status rollback_region_stage(const unsigned long long* heap_used) {
+    ++diag_rollbacks;
     const uint64_t r1 = 1ull << kRegionBits;
     unsigned long long* fill1 = static_cast<unsigned long long*>(d_pfill.ptr);
     const uint8_t* sk_save = static_cast<const uint8_t*>(d_sketch_save.ptr);
@@ -944,6 +959,10 @@ struct dq_freq : Stager {
       DQ_HIP(hipMemsetAsync(hist, 0, kFreqHist * sizeof(unsigned long long), stream));
       DQ_HIP(hipMemsetAsync(ctr() + FC_NBIG, 0, sizeof(unsigned long long), stream));
     }
+    if (!table_empty) {  // (the fused counts are those of an aggregation into an empty table)
+      dev_hist_valid = false;
+      smax_valid = false;
+    }
     DQ_HIP(hipMemsetAsync(ctr() + FC_RETRY, 0, sizeof(unsigned long long), stream));
     // packed records into a fresh table: only the occupied slots are written (the table is
     // compacted; expand() rebuilds the slot image for the operations that probe)
@@ -1011,8 +1030,7 @@ struct dq_freq : Stager {
   bool small_path = true;           // DQ_FREQ_SMALL=0 disables it (tests, A/B)
   uint64_t diag_small_runs = 0;
   dq_status import_runs(std::vector<ImportRun>& runs, int64_t incoming_exact, uint64_t heap_bytes) {
-    invalidate();
-    DQ_TRY(materialize());
+    DQ_TRY(materialize_for_write());
     uint64_t max_n = 0;
     bool general = false;  // a run that may hold keys the LDS image cannot (kind 1 / 2)
     for (const ImportRun& r : runs) {
@@ -1469,7 +1487,9 @@ extern "C" dq_status dq_freq_consume(dq_freq* f, const dq_column* columns, int n
                           f->stream));
     DQ_HIP(hipStreamSynchronize(f->stream));
   }
-  DQ_TRY(f->materialize());
+  // (the batches staged before this one are aggregated first; the fused counts of that aggregation
+  // do not see the rows inserted below)
+  DQ_TRY(f->materialize_for_write());
   if (f->few_groups > 0 && f->ks.n_keys == 1 && f->small_path) {
     // Few groups of one key column (the profiler's low-cardinality histograms): per-workgroup LDS
     // counts, staging lists, one merge (dq_freq_small_kernel).  A key longer than 15 bytes or
@@ -1657,6 +1677,9 @@ extern "C" dq_status dq_diag_freq_paths(dq_freq* f, int64_t* out) {
   out[11] = f->compact ? 1 : 0;
   out[12] = (int64_t)f->diag_uuid_runs;
   out[13] = (int64_t)f->diag_raw16_runs;
+  out[14] = (int64_t)f->diag_rollbacks;
+  out[15] = (int64_t)f->diag_materialized_for_format;
+  out[16] = (int64_t)h[FC_HEAP_USED];  // (read above: the key heap's cursor)
   return DQ_OK;
 }
 
@@ -1857,8 +1880,7 @@ extern "C" dq_status dq_freq_import_flat(dq_freq* f, const int64_t* counts, cons
   if (!f || n < 0 || (n > 0 && (!counts || !key_offsets))) return fail(DQ_ERR_INVALID, "NULL argument");
   if (flags & ~DQ_FLAT_DEVICE) return fail(DQ_ERR_INVALID, "unknown flag");
   DQ_HIP(hipSetDevice(f->ctx->device));
-  f->invalidate();
-  DQ_TRY(f->materialize());
+  DQ_TRY(f->materialize_for_write());
   if (n == 0) {
     f->num_rows += num_rows;
     return DQ_OK;
@@ -1994,8 +2016,7 @@ extern "C" dq_status dq_freq_import(dq_freq* f, const dq_freq_group* groups, int
                                     int64_t num_rows) {
   if (!f || (n > 0 && !groups)) return fail(DQ_ERR_INVALID, "NULL argument");
   DQ_HIP(hipSetDevice(f->ctx->device));
-  f->invalidate();
-  DQ_TRY(f->materialize());
+  DQ_TRY(f->materialize_for_write());
   f->num_rows += num_rows;
   if (n == 0) return DQ_OK;
   // device arrays: ctrl (len | heap flag), count, k0 (inline bytes or offset into the uploaded
@@ -2063,7 +2084,7 @@ extern "C" dq_status dq_freq_merge(dq_freq* dst, dq_freq* src) {
   runs[0] = ImportRun{src->d_slots.ptr, src->capacity, static_cast<const uint8_t*>(src->d_heap.ptr), 2,
                       slice_bits_for(src->capacity), 0, 0};
   if (hs[FC_GROUPS]) DQ_TRY(dst->import_runs(runs, (int64_t)hs[FC_GROUPS], hs[FC_HEAP_USED]));
-  else dst->invalidate();
+  else dst->invalidate();  // (defensive: no group changed, and no cached view depends on num_rows)
   dst->num_rows += src->num_rows;
   return DQ_OK;
 }
@@ -2285,8 +2306,7 @@ extern "C" dq_status dq_freq_import_parts(dq_freq* f, int n_parts, const void* d
     koff += (uint64_t)part_key_bytes[p];
     heap += (uint64_t)part_key_bytes[p];
   }
-  f->invalidate();
-  DQ_TRY(f->materialize());
+  DQ_TRY(f->materialize_for_write());
   f->num_rows += num_rows;
   return f->import_runs(runs, -1, heap);
 }

@@ -33,7 +33,10 @@ dq_status dq_diag_hash_rate(int device, int with_hll, int reps, double* hashes_p
  * globally (slices handed back, tables that already held groups), out[11] = 1 while the table is
  * compacted (occupied slots only), out[12] = partition-path aggregations of canonical UUID records
  * (dq_uuidpack.h), out[13] = partition-path aggregations of 16-byte-key records (16-byte strings,
- * two 8-byte key columns).  `out` holds 14 values. */
+ * two 8-byte key columns), out[14] = batches rolled back out of the staging regions (staged again in
+ * another record format or grouped on the general path), out[15] = times the staged regions were
+ * aggregated because a batch of another record format arrived, out[16] = the key heap's cursor in
+ * bytes (what a rolled-back hashed staging puts back).  `out` holds 17 values. */
 dq_status dq_diag_freq_paths(dq_freq* f, int64_t* out);
 
 /* Test hooks of one table (tests only; never set by the product): flags = 1 makes claimed
