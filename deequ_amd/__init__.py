@@ -34,6 +34,7 @@ from . import kll
 from . import quantiles
 from .arrow import ArrowBatch, ArrowTable
 from .table import Column, PartitionedTable, Table
+from .rowlevel import RowLevelResults, row_level_results
 from .schema import RowLevelSchema, RowLevelSchemaValidationResult, RowLevelSchemaValidator
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -39,6 +39,7 @@ DQ_HLL_NUM_WORDS = 52
 DQ_FREQ_NULL_AS_KEY = 0x1
 DQ_FREQ_FEW_ONLY = 0x2
 DQ_FLAT_DEVICE = 0x1
+DQ_ROWS_FALSE, DQ_ROWS_TRUE, DQ_ROWS_NULL = 1, 2, 4
 
 import re as _re
 
@@ -315,6 +316,13 @@ SIGNATURES = {
     "dq_schema_gather": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "dq_schema_selection": (c_int, [c_void_p, c_int, c_void_p, c_int64]),
     "dq_schema_destroy": (c_int, [c_void_p]),
+    "dq_rows_create": (c_int, [c_void_p, POINTER(DqOp), c_int, POINTER(c_int32), c_int, POINTER(c_void_p)]),
+    "dq_rows_evaluate": (c_int, [c_void_p, POINTER(DqColumn), c_int, c_int64, c_int64, POINTER(c_void_p),
+                                 POINTER(c_void_p)]),
+    "dq_rows_destroy": (c_int, [c_void_p]),
+    "dq_freq_probe_rows": (c_int, [c_void_p, POINTER(DqColumn), c_int, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
+                                   c_void_p]),
+    "dq_rows_select": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, POINTER(c_int64)]),
 }
 
 _lib = None

@@ -2845,3 +2845,6 @@ extern "C" dq_status dq_profile_few_strings(dq_ctx* ctx, int32_t n, const dq_col
 
 // RowLevelSchemaValidator's runner (dq_schema_*) over the kernels of dq_schema.hip.
 #include "dq_schema_api.inc"
+
+// Row-level outcomes (dq_rows_*) over the predicate interpreter, the match masks and dq_rows.hip.
+#include "dq_rows_api.inc"

@@ -1013,6 +1013,58 @@ __global__ __launch_bounds__(kBlock) void dq_freq_linf_kernel(FreqTable X, FreqT
   }
 }
 
+// ---- Row-level probe (dq_freq_probe_rows): which rows of a batch hold a key that is unique in T.
+// One row per lane, one 64-row word per wave and trip: the lane builds its row's key (make_key, the
+// insert path's encoding, hash and per-thread scratch) and probes T read-only, as
+// dq_freq_lookup_kernel's open-addressing branch does -- at most kFreqSliceSlots steps, ending at
+// an empty slot (launch boundary: the table is complete and visible).  A heap reference past the
+// heap is never followed (a loaded state's slots are not trusted).  Rows past the end are clamped to
+// the last row and deselected, so the whole wave reaches the ballot; lane 0 stores the word.
+__global__ __launch_bounds__(kBlock) void dq_freq_probe_rows_kernel(FreqKeySpec ks, const DevColumn* __restrict__ cols,
+                                                                    int64_t n_rows, FreqTable T,
+                                                                    uint64_t* __restrict__ unique_words,
+                                                                    long long* __restrict__ counts) {
+  alignas(8) uint8_t scratch[kMaxLocalKey];
+  const uint32_t lane = threadIdx.x & 63u;
+  const int64_t n_words = (n_rows + 63) >> 6;
+  for (int64_t w = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); w < n_words;
+       w += (int64_t)gridDim.x * (kBlock / 64)) {
+    const int64_t row = (w << 6) + lane;
+    const bool in = row < n_rows;
+    Key k;
+    bool too_long;
+    const bool has = make_key(ks, cols, in ? row : n_rows - 1, k, scratch, too_long) && in;
+    unsigned long long cnt = 0ull;
+    if (has) {
+      const uint32_t tag = tag_of(k.hash);
+      for (uint64_t i = 0; i < kFreqSliceSlots; ++i) {
+        const FreqSlot e = T.slots[probe_slot(T, k.hash, i)];
+        if (e.ctrl == 0ull) break;
+        if ((uint32_t)(e.ctrl >> 32) != tag || (uint32_t)(e.ctrl & kLenMask) != k.len) continue;
+        bool eq;
+        if (k.len <= 16 && !(e.ctrl & kHeapKey)) {
+          eq = e.k0 == k.k0 && e.k1 == k.k1;
+        } else {
+          eq = (e.ctrl & kHeapKey) != 0 && e.k0 <= T.heap_cap && (unsigned long long)k.len <= T.heap_cap - e.k0;
+          const uint8_t* ph = T.heap + e.k0;  // (read only when the reference lies inside the heap)
+          for (uint32_t j = 0; eq && j < k.len; j += 8) {
+            const uint32_t n = k.len - j < 8 ? k.len - j : 8;
+            const uint64_t mine = k.ptr ? ld_partial(k.ptr + j, n) : (j == 0 ? k.k0 : k.k1);
+            eq = ld_partial(ph + j, n) == mine;
+          }
+        }
+        if (eq) {
+          cnt = e.count;
+          break;
+        }
+      }
+    }
+    const uint64_t word = __ballot(cnt == 1ull);
+    if (lane == 0u) unique_words[w] = word;
+    if (counts != nullptr && in) counts[row] = (long long)cnt;
+  }
+}
+
 // ---- MutualInformation (MutualInformation.scala:38-81) over a joint table X of two key columns:
 //   sum over the joint groups of (pxy / total) * log((pxy / total) / ((px / total) * (py / total)))
 // with px / py the sums of the joint counts over each value of key column 0 / 1.  X stays as it
@@ -4994,6 +5046,16 @@ hipError_t launch_freq_linf(const FreqTable& X, const FreqTable& Y, double nx, d
                             unsigned long long* d_common, hipStream_t stream) {
   hipLaunchKernelGGL(dq_freq_linf_kernel, dim3(freq_dist_blocks(X)), dim3(kBlock), 0, stream, X, Y, nx, ny, d_max,
                      d_common);
+  return hipGetLastError();
+}
+
+hipError_t launch_freq_probe_rows(const FreqKeySpec& ks, const DevColumn* d_cols, int64_t n_rows, const FreqTable& T,
+                                  uint64_t* d_unique, long long* d_counts, hipStream_t stream) {
+  if (n_rows <= 0) return hipSuccess;
+  const int64_t n_words = (n_rows + 63) >> 6;
+  const int64_t blocks = std::min<int64_t>((n_words + 3) / 4, kFreqProbeMaxBlocks);
+  hipLaunchKernelGGL(dq_freq_probe_rows_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, stream, ks, d_cols, n_rows, T,
+                     d_unique, d_counts);
   return hipGetLastError();
 }
 

@@ -114,6 +114,7 @@ struct dq_freq : Stager {
   // dq_freq_export_flat's device result, kept from the sizing call to the filling call
   DevBuf d_flat_aux, d_flat, d_flat_bytes;
   DevBuf d_dist;  // dq_freq_linf_distance's eight result words
+  DevBuf d_probe;  // dq_freq_probe_rows' "count == 1" words of the batch
   bool flat_valid = false;
   uint64_t flat_n = 0, flat_bytes = 0;
   void invalidate() {
@@ -2009,6 +2010,48 @@ extern "C" dq_status dq_freq_lookup(dq_freq* f, const uint8_t* key, int64_t key_
   unsigned long long h[FC_COUNT];
   DQ_TRY(f->read_counters(h));
   *count = (int64_t)h[FC_EXPORT_N];
+  return DQ_OK;
+}
+
+// Row-level outcomes of Uniqueness (include/deequ_amd.h "row-level outcomes"): see dq_freq.hip
+// "Row-level probe" and dq_rows.hip.  The table is materialised first and its stream is idle
+// (read_counters) before the probe's launch reads the slot image.
+extern "C" dq_status dq_freq_probe_rows(dq_freq* f, const dq_column* columns, int n_columns, int64_t n_rows,
+                                        const uint64_t* d_selected, int64_t out_bit_offset, uint64_t* d_value,
+                                        uint64_t* d_valid, int64_t* d_counts) {
+  if (!f) return fail(DQ_ERR_INVALID, "NULL table");
+  if (f->ks.null_as_key)
+    return fail(DQ_ERR_INVALID, "dq_freq_probe_rows: a DQ_FREQ_NULL_AS_KEY (Histogram) table groups its NULLs, so "
+                                "\"count == 1\" there is not Uniqueness's outcome");
+  if (n_columns != (int)f->col_types.size()) return fail(DQ_ERR_INVALID, "column count differs from the table");
+  if (n_rows < 0 || out_bit_offset < 0) return fail(DQ_ERR_INVALID, "negative n_rows or out_bit_offset");
+  if (n_rows == 0) return DQ_OK;
+  if (!columns || !d_value || !d_valid) return fail(DQ_ERR_INVALID, "NULL argument");
+  if (f->few_failed) return fail(DQ_ERR_SPACE, "DQ_FREQ_FEW_ONLY: the column has more groups than the few-groups path holds");
+  DQ_HIP(hipSetDevice(f->ctx->device));
+  DQ_TRY(f->materialize());
+  unsigned long long h[FC_COUNT];
+  DQ_TRY(f->read_counters(h));
+  const size_t words = (size_t)((n_rows + 63) >> 6);
+  DQ_TRY(f->d_probe.ensure(words * sizeof(uint64_t)));
+  uint64_t* unique = static_cast<uint64_t*>(f->d_probe.ptr);
+  if (h[FC_GROUPS] == 0) {  // (no group: no key is in the table, and its slot image may not exist yet)
+    DQ_HIP(hipMemsetAsync(unique, 0, words * sizeof(uint64_t), f->stream));
+    if (d_counts) DQ_HIP(hipMemsetAsync(d_counts, 0, (size_t)n_rows * sizeof(int64_t), f->stream));
+  } else {
+    for (int c = 0; c < n_columns; ++c) std::memset(&f->h_cols[c], 0, sizeof(DevColumn));
+    for (int i = 0; i < f->ks.n_keys; ++i) {  // (the key columns only: a filtered table's other columns are not read)
+      const int c = f->ks.key_cols[i];
+      DQ_TRY(prepare_column(f, c, columns[c], n_rows, &f->h_cols[c]));
+    }
+    DQ_HIP(hipMemcpyAsync(f->d_cols.ptr, f->h_cols.data(), n_columns * sizeof(DevColumn), hipMemcpyHostToDevice,
+                          f->stream));
+    DQ_HIP(launch_freq_probe_rows(f->ks, static_cast<const DevColumn*>(f->d_cols.ptr), n_rows, f->view(), unique,
+                                  reinterpret_cast<long long*>(d_counts), f->stream));
+  }
+  DQ_HIP(launch_rows_combine(nullptr, unique, d_selected, n_rows, out_bit_offset, d_value, d_valid, f->stream));
+  DQ_HIP(hipStreamSynchronize(f->stream));
+  f->host_tmp.clear();
   return DQ_OK;
 }
 

@@ -391,6 +391,30 @@ constexpr unsigned kFreqDistMaxBlocks = 2048;  // the passes' grid cap (kBlock s
 hipError_t launch_freq_totals(const FreqTable& T, unsigned long long* d_tot, hipStream_t stream);
 hipError_t launch_freq_linf(const FreqTable& X, const FreqTable& Y, double nx, double ny, unsigned long long* d_max,
                             unsigned long long* d_common, hipStream_t stream);
+// Row-level outcomes (dq_freq_probe_rows, dq_freq.hip "Row-level probe"): every row of the batch
+// builds its key and probes T; bit r of d_unique (ceil(n_rows / 64) words, every bit at and past
+// n_rows 0) = row r's key has count 1, d_counts[r] (nullptr: not wanted) = its count (0: no key, or
+// not in T).  Same geometry as launch_predicates.
+constexpr int64_t kFreqProbeMaxBlocks = 2048;
+hipError_t launch_freq_probe_rows(const FreqKeySpec& ks, const DevColumn* d_cols, int64_t n_rows, const FreqTable& T,
+                                  uint64_t* d_unique, long long* d_counts, hipStream_t stream);
+// dq_rows.hip.  combine: value = condition & selected, valid = selected over n_rows rows, written
+// at bit out_off of the two bitmaps (the other bits of the edge words are kept).  The condition is
+// a byte-aligned Arrow bitmap at bit 0 (cond_bytes: a column's validity), else 64-bit words
+// (cond_words: a predicate's TRUE plane, a match mask, the probe's bits), else all ones; selected
+// is sel_words or all ones.  Source bits at and past n_rows are not read as set.
+hipError_t launch_rows_combine(const uint8_t* cond_bytes, const uint64_t* cond_words, const uint64_t* sel_words,
+                               int64_t n_rows, int64_t out_off, uint64_t* d_value, uint64_t* d_valid,
+                               hipStream_t stream);
+// select: d_counts[w] = the picked bits (DQ_ROWS_* of `which`) of word w, d_counts[n_words] = 0;
+// after an exclusive scan of those n_words + 1 values, the rows' indices go to d_out in ascending
+// order (an index at or past `capacity` is dropped).
+constexpr int64_t kRowsSelectMaxBlocks = 2048;
+hipError_t launch_rows_select_count(const uint64_t* d_value, const uint64_t* d_valid, int64_t n_rows, int which,
+                                    unsigned long long* d_counts, hipStream_t stream);
+hipError_t launch_rows_select_scatter(const uint64_t* d_value, const uint64_t* d_valid, int64_t n_rows, int which,
+                                      const unsigned long long* d_base, int64_t* d_out, int64_t capacity,
+                                      hipStream_t stream);
 // MutualInformation (dq_freq_mutual_information, dq_freq.hip "MutualInformation") over the joint
 // table X of two key columns of types type_a / type_b (DQ_T_*).  project: every group of X adds its
 // count to its two fields' groups in the empty marginal tables TA / TB; *d_flags |= kMiBadKey /

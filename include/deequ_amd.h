@@ -823,6 +823,51 @@ dq_status dq_schema_gather(dq_schema* s, int which, int column, void* values, vo
 dq_status dq_schema_selection(dq_schema* s, int which, int32_t* out, int64_t capacity);
 dq_status dq_schema_destroy(dq_schema* s);
 
+/* ---------------------------------------------------------------- row-level outcomes
+ * Which rows an analyzer counts.  Every outcome is one nullable boolean per row, held as two device
+ * bitmaps in the Arrow boolean layout (LSB first, whole 64-bit words): `value` (bit = TRUE) and
+ * `valid` (bit = not NULL).  A row that the op's `where` does not select (FALSE or NULL) is NULL;
+ * a selected row is TRUE where
+ *   DQ_OP_COMPLETENESS   the column is not NULL,
+ *   DQ_OP_COMPLIANCE     the predicate is TRUE (a NULL predicate is FALSE),
+ *   DQ_OP_PATTERN_MATCH  the value holds a non-empty match (a NULL value is FALSE),
+ *   dq_freq_probe_rows   the row's key has count exactly 1 in the table probed (a NULL key column
+ *                        and a key absent from the table are FALSE),
+ * so popcount(value) is the numerator and popcount(valid) the denominator of the state the same op
+ * (or the table's group-by) yields over the same rows.
+ *
+ * A batch writes its n_rows outcomes at bit `out_bit_offset` of the caller's bitmaps (its row offset
+ * in a bitmap pair that spans several batches): bits [out_bit_offset, out_bit_offset + n_rows).  The
+ * other bits of the first and last word touched keep their values, so the caller zeroes the bitmaps
+ * once; batches that share a word are evaluated one after the other.  Every call is synchronous. */
+typedef struct dq_rows dq_rows;
+/* Ops: DQ_OP_COMPLETENESS, DQ_OP_COMPLIANCE, DQ_OP_PATTERN_MATCH (anything else is DQ_ERR_INVALID),
+ * each checked as dq_op_supported checks it. */
+dq_status dq_rows_create(dq_ctx* ctx, const dq_op* ops, int n_ops, const int32_t* column_types, int n_columns,
+                         dq_rows** out);
+/* d_value[i] / d_valid[i]: op i's device bitmaps. */
+dq_status dq_rows_evaluate(dq_rows* rows, const dq_column* columns, int n_columns, int64_t n_rows,
+                           int64_t out_bit_offset, uint64_t* const* d_value, uint64_t* const* d_valid);
+dq_status dq_rows_destroy(dq_rows* rows);
+/* Probes the table (read only; any staged rows are aggregated first) with the key of every row of
+ * the batch, whose columns are the table's.  d_selected (NULL: every row) is a device bitmap at bit
+ * 0 of the rows a `where` selects, (n_rows + 63) / 64 words, e.g. the `value` bitmap of a
+ * DQ_OP_COMPLIANCE outcome of the filter.  d_counts (NULL: not wanted) receives n_rows counts, 0
+ * for a row without a key or with a key the table does not hold, whatever d_selected says.
+ * A DQ_FREQ_NULL_AS_KEY table is DQ_ERR_INVALID. */
+dq_status dq_freq_probe_rows(dq_freq* f, const dq_column* columns, int n_columns, int64_t n_rows,
+                             const uint64_t* d_selected, int64_t out_bit_offset, uint64_t* d_value,
+                             uint64_t* d_valid, int64_t* d_counts);
+/* The ascending row indices of the outcomes named by `which` (an OR of DQ_ROWS_*) among the first
+ * n_rows bits of a bitmap pair, into the device array d_out; *n_out = how many there are.  When
+ * that is above `capacity` (entries) nothing is written and the call returns DQ_ERR_SPACE: a call
+ * with capacity 0 counts. */
+#define DQ_ROWS_FALSE 1
+#define DQ_ROWS_TRUE 2
+#define DQ_ROWS_NULL 4
+dq_status dq_rows_select(dq_ctx* ctx, const uint64_t* d_value, const uint64_t* d_valid, int64_t n_rows, int which,
+                         int64_t* d_out, int64_t capacity, int64_t* n_out);
+
 #ifdef __cplusplus
 }
 #endif
