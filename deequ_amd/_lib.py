@@ -136,6 +136,10 @@ class DqFreqDistance(Structure):
                 ("groups_b", c_int64), ("groups_common", c_int64)]
 
 
+class DqMatchCounts(Structure):
+    _fields_ = [("matched", c_int64), ("key_null", c_int64), ("key_absent", c_int64), ("cells_differ", c_int64)]
+
+
 class DqFreqMi(Structure):
     _fields_ = [("mi", c_double), ("num_rows", c_int64), ("groups", c_int64), ("groups_a", c_int64),
                 ("groups_b", c_int64)]
@@ -197,6 +201,7 @@ DIAG_SIGNATURES = {
     "dq_diag_key_pack": (c_int, [c_char_p, c_int32, POINTER(c_uint64), c_char_p, POINTER(c_int32), POINTER(c_int32)]),
     "dq_diag_uuid_pack": (c_int, [c_char_p, c_int32, POINTER(c_uint64), c_char_p, POINTER(c_int32)]),
     "dq_diag_eval_predicate": (c_int, [POINTER(DqPredicate), POINTER(DqColumn), c_int, c_int64, c_void_p]),
+    "dq_diag_cell_equal": (c_int, [POINTER(DqColumn), c_int64, POINTER(DqColumn), c_int64, POINTER(c_int32)]),
     "dq_diag_regex_match": (c_int, [c_char_p, c_int32, c_char_p, c_int64, POINTER(c_int32), POINTER(c_int32),
                                     POINTER(c_int32)]),
     "dq_diag_regex_match_mode": (c_int, [c_char_p, c_int32, c_int32, c_char_p, c_int64, POINTER(c_int32),
@@ -323,6 +328,10 @@ SIGNATURES = {
     "dq_freq_probe_rows": (c_int, [c_void_p, POINTER(DqColumn), c_int, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
                                    c_void_p]),
     "dq_rows_select": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_int64, POINTER(c_int64)]),
+    "dq_freq_index_rows": (c_int, [c_void_p, POINTER(DqColumn), c_int, c_int64, c_int64]),
+    "dq_freq_match_rows": (c_int, [c_void_p, POINTER(DqColumn), c_int, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
+                                   POINTER(DqColumn), POINTER(DqColumn), c_int, c_int64, c_void_p,
+                                   POINTER(DqMatchCounts)]),
 }
 
 _lib = None

@@ -2507,6 +2507,27 @@ extern "C" dq_status dq_diag_eval_predicate(const dq_predicate* p, const dq_colu
   return DQ_OK;
 }
 
+// Host build of the cross-table checks' cell equality (dq_celleq.h, the same source
+// dq_freq_match_rows_kernel runs).  The header names the type codes itself, to stand alone.
+static_assert(celleq::T_BOOL == DQ_T_BOOL && celleq::T_INT8 == DQ_T_INT8 && celleq::T_INT16 == DQ_T_INT16 &&
+                  celleq::T_INT32 == DQ_T_INT32 && celleq::T_INT64 == DQ_T_INT64 && celleq::T_FLOAT32 == DQ_T_FLOAT32 &&
+                  celleq::T_FLOAT64 == DQ_T_FLOAT64 && celleq::T_UTF8 == DQ_T_UTF8 &&
+                  celleq::T_DECIMAL128 == DQ_T_DECIMAL128,
+              "dq_celleq.h's type codes are dq_type's");
+extern "C" dq_status dq_diag_cell_equal(const dq_column* a, int64_t i, const dq_column* b, int64_t j, int32_t* equal) {
+  if (!a || !b || !equal) return fail(DQ_ERR_INVALID, "bad argument");
+  if ((a->flags | b->flags) & DQ_COL_DEVICE) return fail(DQ_ERR_INVALID, "host columns only");
+  if (a->type != b->type || !valid_type(a->type)) return fail(DQ_ERR_INVALID, "the two columns have different types");
+  if (i < 0 || i >= a->length || j < 0 || j >= b->length || a->offset < 0 || b->offset < 0)
+    return fail(DQ_ERR_INVALID, "row outside its column");
+  if (!a->values || !b->values || ((a->type & 0xff) == DQ_T_UTF8 && (!a->offsets || !b->offsets)))
+    return fail(DQ_ERR_INVALID, "column without values or offsets");
+  const celleq::Cells ca{a->validity, a->values, a->offsets, a->type, 0, a->offset};
+  const celleq::Cells cb{b->validity, b->values, b->offsets, b->type, 0, b->offset};
+  *equal = celleq::cell_equal(ca, i, cb, j) ? 1 : 0;
+  return DQ_OK;
+}
+
 // Host build of the group-by's digit-key packing (dq_keypack.h): the record word of a key of
 // <= 15 bytes, and the key bytes it unpacks to.
 extern "C" dq_status dq_diag_key_pack(const uint8_t* key, int32_t len, uint64_t* packed, uint8_t* back,

@@ -1065,6 +1065,147 @@ __global__ __launch_bounds__(kBlock) void dq_freq_probe_rows_kernel(FreqKeySpec 
   }
 }
 
+// ---- Cross-table checks (dq_freq_index_rows, dq_freq_match_rows): T is the group-by of the
+// reference table B's key columns, materialised, so a key's slot does not move until the table
+// changes.  row_of_slot (one int64 per slot, -1 = no row) maps a slot to the row of B that holds its
+// key; the match follows it from a row of the primary table A and compares cells across the tables.
+
+// Slot e of T holds key k (the row-level probe's comparison: a heap reference past the heap is never
+// followed).
+__device__ inline bool slot_holds(const FreqTable& T, const FreqSlot& e, const Key& k, uint32_t tag) {
+  if ((uint32_t)(e.ctrl >> 32) != tag || (uint32_t)(e.ctrl & kLenMask) != k.len) return false;
+  if (k.len <= 16 && !(e.ctrl & kHeapKey)) return e.k0 == k.k0 && e.k1 == k.k1;
+  bool eq = (e.ctrl & kHeapKey) != 0 && e.k0 <= T.heap_cap && (unsigned long long)k.len <= T.heap_cap - e.k0;
+  const uint8_t* ph = T.heap + e.k0;  // (read only when the reference lies inside the heap)
+  for (uint32_t j = 0; eq && j < k.len; j += 8) {
+    const uint32_t n = k.len - j < 8 ? k.len - j : 8;
+    const uint64_t mine = k.ptr ? ld_partial(k.ptr + j, n) : (j == 0 ? k.k0 : k.k1);
+    eq = ld_partial(ph + j, n) == mine;
+  }
+  return eq;
+}
+
+// One row of B per lane, in the probe's geometry: the row's key is built and looked up read-only,
+// and its row number goes into its slot's entry.  With unique keys every entry has one writer (plain
+// stores); with duplicates any one of the key's rows stays, each a valid row.  A NULL key is skipped;
+// a key T does not hold is counted (the batch is not what T was built from).  s < capacity by
+// probe_slot's mask, and row_of_slot has one entry per slot.
+__global__ __launch_bounds__(kBlock) void dq_freq_index_rows_kernel(FreqKeySpec ks, const DevColumn* __restrict__ cols,
+                                                                    int64_t n_rows, FreqTable T,
+                                                                    long long* __restrict__ row_of_slot,
+                                                                    int64_t row_offset,
+                                                                    unsigned long long* __restrict__ n_absent) {
+  alignas(8) uint8_t scratch[kMaxLocalKey];
+  const uint32_t lane = threadIdx.x & 63u;
+  const int64_t n_words = (n_rows + 63) >> 6;
+  unsigned long long absent = 0ull;  // (wave-uniform)
+  for (int64_t w = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); w < n_words;
+       w += (int64_t)gridDim.x * (kBlock / 64)) {
+    const int64_t row = (w << 6) + lane;
+    const bool in = row < n_rows;
+    Key k;
+    bool too_long;
+    const bool has = make_key(ks, cols, in ? row : n_rows - 1, k, scratch, too_long) && in;
+    bool hit = false;
+    if (has) {
+      const uint32_t tag = tag_of(k.hash);
+      for (uint64_t i = 0; i < kFreqSliceSlots; ++i) {
+        const uint64_t s = probe_slot(T, k.hash, i);
+        const FreqSlot e = T.slots[s];
+        if (e.ctrl == 0ull) break;
+        if (!slot_holds(T, e, k, tag)) continue;
+        row_of_slot[s] = (long long)(row_offset + row);
+        hit = true;
+        break;
+      }
+    }
+    absent += (unsigned long long)__popcll(__ballot((has && !hit) || (in && too_long)));
+  }
+  if (lane == 0u && absent != 0ull) atomicAdd(n_absent, absent);
+}
+
+// One row of A per lane, one 64-row word per wave and trip: make_key, the probe, and on a hit the
+// row j of B from row_of_slot, then the compare pairs' cell equality (dq_celleq.h) between row
+// `row` of A and row j of B.  The dependent chain of a hit is slot -> row_of_slot -> B's cells; the
+// entry of the first probe position shares the slot's index, so it is loaded with that slot (both
+// loads are issued before either is used) and the chain is one HBM miss shorter for every key
+// that sits at its first position.  j is followed only inside [0, b_rows): an entry that no indexed
+// row wrote (-1) makes the key absent.  row_of_slot == nullptr (no compare pair, no reference_rows
+// wanted): the hit alone decides.  Rows past the end are clamped and deselected, so the whole wave
+// reaches the ballots; lane 0 stores the word of the "matched" plane, which dq_rows_combine_kernel
+// shifts to the batch's bit offset.  counts[0..3] = TRUE, NULL key, absent key, differing cells
+// among the selected rows: per wave in registers, per workgroup through LDS, one atomic each.
+__global__ __launch_bounds__(kBlock) void dq_freq_match_rows_kernel(
+    FreqKeySpec ks, const DevColumn* __restrict__ cols, int64_t n_rows, FreqTable T,
+    const uint64_t* __restrict__ selected, const long long* __restrict__ row_of_slot, int64_t b_rows,
+    const celleq::Cells* __restrict__ a_cmp, const celleq::Cells* __restrict__ b_cmp, int n_pairs,
+    uint64_t* __restrict__ matched_words, long long* __restrict__ reference_rows,
+    unsigned long long* __restrict__ counts) {
+  alignas(8) uint8_t scratch[kMaxLocalKey];
+  __shared__ unsigned long long part[kBlock / 64][4];
+  const uint32_t lane = threadIdx.x & 63u;
+  const int64_t n_words = (n_rows + 63) >> 6;
+  unsigned long long c_true = 0ull, c_null = 0ull, c_absent = 0ull, c_differ = 0ull;  // (wave-uniform)
+  for (int64_t w = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6); w < n_words;
+       w += (int64_t)gridDim.x * (kBlock / 64)) {
+    const int64_t row = (w << 6) + lane;
+    const bool in = row < n_rows;
+    Key k;
+    bool too_long;
+    const bool has = make_key(ks, cols, in ? row : n_rows - 1, k, scratch, too_long) && in;
+    bool hit = false;
+    long long j = -1;
+    if (has) {
+      const uint32_t tag = tag_of(k.hash);
+      const uint64_t s0 = probe_slot(T, k.hash, 0);
+      const long long j0 = row_of_slot != nullptr ? row_of_slot[s0] : -1;  // (issued with the slot's load below)
+      for (uint64_t i = 0; i < kFreqSliceSlots; ++i) {
+        const uint64_t s = i == 0 ? s0 : probe_slot(T, k.hash, i);
+        const FreqSlot e = T.slots[s];
+        if (e.ctrl == 0ull) break;
+        if (!slot_holds(T, e, k, tag)) continue;
+        hit = true;
+        if (row_of_slot != nullptr) {
+          j = i == 0 ? j0 : row_of_slot[s];
+          if (j < 0 || j >= b_rows) {
+            hit = false;
+            j = -1;
+          }
+        }
+        break;
+      }
+    }
+    bool eq = hit;
+    for (int p = 0; p < n_pairs; ++p)
+      if (eq) eq = celleq::cell_equal(a_cmp[p], row, b_cmp[p], j);
+    const int64_t rest = n_rows - (w << 6);
+    const uint64_t sel = (selected != nullptr ? selected[w] : ~0ull) & (rest < 64 ? (1ull << rest) - 1ull : ~0ull);
+    const uint64_t m_true = __ballot(eq);
+    const uint64_t m_null = __ballot(in && !has);
+    const uint64_t m_absent = __ballot(has && !hit);
+    const uint64_t m_differ = __ballot(hit && !eq);
+    if (lane == 0u) matched_words[w] = m_true;
+    c_true += (unsigned long long)__popcll(m_true & sel);
+    c_null += (unsigned long long)__popcll(m_null & sel);
+    c_absent += (unsigned long long)__popcll(m_absent & sel);
+    c_differ += (unsigned long long)__popcll(m_differ & sel);
+    if (reference_rows != nullptr && in) reference_rows[row] = j;
+  }
+  if (lane == 0u) {
+    unsigned long long* mine = part[threadIdx.x >> 6];
+    mine[0] = c_true;
+    mine[1] = c_null;
+    mine[2] = c_absent;
+    mine[3] = c_differ;
+  }
+  __syncthreads();
+  if (threadIdx.x < 4u) {
+    unsigned long long sum = 0ull;
+    for (int v = 0; v < kBlock / 64; ++v) sum += part[v][threadIdx.x];
+    if (sum != 0ull) atomicAdd(counts + threadIdx.x, sum);
+  }
+}
+
 // ---- MutualInformation (MutualInformation.scala:38-81) over a joint table X of two key columns:
 //   sum over the joint groups of (pxy / total) * log((pxy / total) / ((px / total) * (py / total)))
 // with px / py the sums of the joint counts over each value of key column 0 / 1.  X stays as it
@@ -5056,6 +5197,32 @@ hipError_t launch_freq_probe_rows(const FreqKeySpec& ks, const DevColumn* d_cols
   const int64_t blocks = std::min<int64_t>((n_words + 3) / 4, kFreqProbeMaxBlocks);
   hipLaunchKernelGGL(dq_freq_probe_rows_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, stream, ks, d_cols, n_rows, T,
                      d_unique, d_counts);
+  return hipGetLastError();
+}
+
+hipError_t launch_freq_index_rows(const FreqKeySpec& ks, const DevColumn* d_cols, int64_t n_rows, const FreqTable& T,
+                                  long long* d_row_of_slot, int64_t row_offset, unsigned long long* d_absent,
+                                  hipStream_t stream) {
+  if (n_rows <= 0) return hipSuccess;
+  const int64_t n_words = (n_rows + 63) >> 6;
+  const int64_t blocks = std::min<int64_t>((n_words + 3) / 4, kFreqProbeMaxBlocks);
+  hipLaunchKernelGGL(dq_freq_index_rows_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, stream, ks, d_cols, n_rows, T,
+                     d_row_of_slot, row_offset, d_absent);
+  return hipGetLastError();
+}
+
+hipError_t launch_freq_match_rows(const FreqKeySpec& ks, const DevColumn* d_cols, int64_t n_rows, const FreqTable& T,
+                                  const uint64_t* d_selected, const long long* d_row_of_slot, int64_t b_rows,
+                                  const celleq::Cells* d_a_cmp, const celleq::Cells* d_b_cmp, int n_pairs,
+                                  uint64_t* d_matched, long long* d_reference_rows, unsigned long long* d_counts,
+                                  hipStream_t stream) {
+  if (n_rows <= 0) return hipSuccess;
+  if (d_row_of_slot == nullptr && (n_pairs > 0 || d_reference_rows != nullptr)) return hipErrorInvalidValue;
+  const int64_t n_words = (n_rows + 63) >> 6;
+  const int64_t blocks = std::min<int64_t>((n_words + 3) / 4, kFreqProbeMaxBlocks);
+  hipLaunchKernelGGL(dq_freq_match_rows_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, stream, ks, d_cols, n_rows, T,
+                     d_selected, d_row_of_slot, b_rows, d_a_cmp, d_b_cmp, n_pairs, d_matched, d_reference_rows,
+                     d_counts);
   return hipGetLastError();
 }
 

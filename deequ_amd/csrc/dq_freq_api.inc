@@ -117,7 +117,19 @@ struct dq_freq : Stager {
   DevBuf d_probe;  // dq_freq_probe_rows' "count == 1" words of the batch
   bool flat_valid = false;
   uint64_t flat_n = 0, flat_bytes = 0;
+  // Cross-table checks: d_row_of_slot[s] = the row (dq_freq_index_rows) that holds slot s's key, -1
+  // where none was indexed; one int64 per slot, alive while index_valid.  A slot keeps its place
+  // only until the table changes, so whatever changes it or moves its slots drops the index.
+  // d_match: the index's absent counter, the match's four counters, then its compare columns.
+  static constexpr size_t kMatchHeadBytes = 64;
+  DevBuf d_row_of_slot, d_match;
+  bool index_valid = false;
+  void drop_index() {
+    index_valid = false;
+    d_row_of_slot.release();
+  }
   void invalidate() {
+    drop_index();
     flat_valid = false;
     hist_valid = false;
     dev_hist_valid = false;
@@ -226,6 +238,7 @@ struct dq_freq : Stager {
     d_slots.swap(fresh);
     compact = false;
     table_cleared = true;
+    drop_index();
     return DQ_OK;
   }
 
@@ -254,6 +267,7 @@ struct dq_freq : Stager {
     DQ_HIP(hipStreamSynchronize(stream));
     d_slots.swap(fresh);
     capacity = cap;
+    drop_index();
     return DQ_OK;
   }
 
@@ -2052,6 +2066,126 @@ extern "C" dq_status dq_freq_probe_rows(dq_freq* f, const dq_column* columns, in
   DQ_HIP(launch_rows_combine(nullptr, unique, d_selected, n_rows, out_bit_offset, d_value, d_valid, f->stream));
   DQ_HIP(hipStreamSynchronize(f->stream));
   f->host_tmp.clear();
+  return DQ_OK;
+}
+
+// Cross-table checks (include/deequ_amd.h "cross-table checks"): dq_freq.hip "Cross-table checks".
+// Both calls materialise the table and leave its stream idle (read_counters) before their launch
+// reads the slot image; a table without groups has its image cleared first (an aggregation that
+// found no key may have left it unwritten), so the kernels run on it as on any other.
+static dq_status cross_prepare(dq_freq* f, const dq_column* columns, int n_columns, int64_t n_rows, const char* who) {
+  if (f->ks.null_as_key)
+    return fail(DQ_ERR_INVALID, std::string(who) + ": a DQ_FREQ_NULL_AS_KEY (Histogram) table groups its NULLs, so "
+                                                   "\"the table holds the key\" is not a join's condition there");
+  if (n_columns != (int)f->col_types.size()) return fail(DQ_ERR_INVALID, "column count differs from the table");
+  if (f->few_failed) return fail(DQ_ERR_SPACE, "DQ_FREQ_FEW_ONLY: the column has more groups than the few-groups path holds");
+  DQ_HIP(hipSetDevice(f->ctx->device));
+  DQ_TRY(f->materialize());
+  unsigned long long h[FC_COUNT];
+  DQ_TRY(f->read_counters(h));
+  if (h[FC_GROUPS] == 0) DQ_TRY(f->clear_table());
+  for (int c = 0; c < n_columns; ++c) std::memset(&f->h_cols[c], 0, sizeof(DevColumn));
+  for (int i = 0; i < f->ks.n_keys; ++i) {  // (the key columns only)
+    const int c = f->ks.key_cols[i];
+    DQ_TRY(prepare_column(f, c, columns[c], n_rows, &f->h_cols[c]));
+  }
+  DQ_HIP(hipMemcpyAsync(f->d_cols.ptr, f->h_cols.data(), n_columns * sizeof(DevColumn), hipMemcpyHostToDevice,
+                        f->stream));
+  return DQ_OK;
+}
+
+extern "C" dq_status dq_freq_index_rows(dq_freq* f, const dq_column* columns, int n_columns, int64_t n_rows,
+                                        int64_t row_offset) {
+  if (!f) return fail(DQ_ERR_INVALID, "NULL table");
+  if (n_rows < 0 || row_offset < 0) return fail(DQ_ERR_INVALID, "negative n_rows or row_offset");
+  if (n_rows > 0 && !columns) return fail(DQ_ERR_INVALID, "NULL argument");
+  if (f->filtered)
+    return fail(DQ_ERR_INVALID, "dq_freq_index_rows: a filtered table does not hold the keys of the rows its filter "
+                                "dropped, so the batch is not what it was built from");
+  DQ_TRY(cross_prepare(f, columns, n_columns, n_rows, "dq_freq_index_rows"));
+  if (!f->index_valid) {  // (first call since the table last changed: one entry per slot, all -1)
+    DQ_TRY(f->d_row_of_slot.ensure((size_t)f->capacity * sizeof(int64_t)));
+    DQ_HIP(hipMemsetAsync(f->d_row_of_slot.ptr, 0xff, (size_t)f->capacity * sizeof(int64_t), f->stream));
+    f->index_valid = true;
+  }
+  DQ_TRY(f->d_match.ensure(dq_freq::kMatchHeadBytes));
+  unsigned long long* d_absent = static_cast<unsigned long long*>(f->d_match.ptr);
+  DQ_HIP(hipMemsetAsync(d_absent, 0, sizeof(unsigned long long), f->stream));
+  DQ_HIP(launch_freq_index_rows(f->ks, static_cast<const DevColumn*>(f->d_cols.ptr), n_rows, f->view(),
+                                static_cast<long long*>(f->d_row_of_slot.ptr), row_offset, d_absent, f->stream));
+  unsigned long long absent = 0;
+  DQ_HIP(hipMemcpyAsync(&absent, d_absent, sizeof(absent), hipMemcpyDeviceToHost, f->stream));
+  DQ_HIP(hipStreamSynchronize(f->stream));
+  f->host_tmp.clear();
+  if (absent != 0) {
+    f->drop_index();
+    return fail(DQ_ERR_STATE, "dq_freq_index_rows: " + std::to_string(absent) + " rows hold a key the table does not: "
+                              "the batch is not what the table was built from");
+  }
+  return DQ_OK;
+}
+
+static dq_status compare_cells(const dq_column& col, int64_t rows, const char* side, int p, celleq::Cells* out) {
+  const std::string who = std::string("dq_freq_match_rows: ") + side + " compare column " + std::to_string(p);
+  if (!valid_type(col.type)) return fail(DQ_ERR_INVALID, who + " has an invalid type");
+  if (!(col.flags & DQ_COL_DEVICE)) return fail(DQ_ERR_INVALID, who + " is not DQ_COL_DEVICE (compare columns are read in place)");
+  if (col.length < rows || col.offset < 0) return fail(DQ_ERR_INVALID, who + " is shorter than its table, or its offset is negative");
+  if (rows > 0 && !col.values) return fail(DQ_ERR_INVALID, who + " has no values");
+  if ((col.type & 0xff) == DQ_T_UTF8 && !col.offsets) return fail(DQ_ERR_INVALID, who + " is utf8 without offsets");
+  *out = celleq::Cells{col.validity, col.values, col.offsets, col.type, 0, col.offset};
+  return DQ_OK;
+}
+
+extern "C" dq_status dq_freq_match_rows(dq_freq* f, const dq_column* columns, int n_columns, int64_t n_rows,
+                                        const uint64_t* d_selected, int64_t out_bit_offset, uint64_t* d_value,
+                                        uint64_t* d_valid, const dq_column* a_compare, const dq_column* b_compare,
+                                        int n_pairs, int64_t b_rows, int64_t* d_reference_rows,
+                                        dq_match_counts* counts) {
+  if (!f) return fail(DQ_ERR_INVALID, "NULL table");
+  if (n_rows < 0 || out_bit_offset < 0 || n_pairs < 0 || b_rows < 0)
+    return fail(DQ_ERR_INVALID, "negative n_rows, out_bit_offset, n_pairs or b_rows");
+  if (n_pairs > DQ_MATCH_MAX_PAIRS) return fail(DQ_ERR_UNSUPPORTED, "more than 32 compare pairs");
+  if (n_pairs > 0 && (!a_compare || !b_compare)) return fail(DQ_ERR_INVALID, "NULL compare columns");
+  if (n_rows == 0) return DQ_OK;
+  if (!columns || !d_value || !d_valid) return fail(DQ_ERR_INVALID, "NULL argument");
+  std::vector<celleq::Cells> cells((size_t)2 * n_pairs);
+  for (int p = 0; p < n_pairs; ++p) {
+    if (a_compare[p].type != b_compare[p].type)
+      return fail(DQ_ERR_INVALID, "dq_freq_match_rows: compare pair " + std::to_string(p) + " has two types");
+    DQ_TRY(compare_cells(a_compare[p], n_rows, "primary", p, &cells[p]));
+    DQ_TRY(compare_cells(b_compare[p], b_rows, "reference", p, &cells[n_pairs + p]));
+  }
+  const bool follow = n_pairs > 0 || d_reference_rows != nullptr;
+  if (follow && !f->index_valid)
+    return fail(DQ_ERR_STATE, "dq_freq_match_rows: compare pairs and reference rows need dq_freq_index_rows after the "
+                              "table last changed");
+  DQ_TRY(cross_prepare(f, columns, n_columns, n_rows, "dq_freq_match_rows"));
+  if (follow && !f->index_valid) return fail(DQ_ERR_STATE, "dq_freq_match_rows: the table changed under its row index");
+  const size_t words = (size_t)((n_rows + 63) >> 6);
+  DQ_TRY(f->d_probe.ensure(words * sizeof(uint64_t)));
+  DQ_TRY(f->d_match.ensure(dq_freq::kMatchHeadBytes + cells.size() * sizeof(celleq::Cells)));
+  uint8_t* base = static_cast<uint8_t*>(f->d_match.ptr);
+  unsigned long long* d_counts = reinterpret_cast<unsigned long long*>(base) + 1;  // (word 0: the index's counter)
+  celleq::Cells* d_cells = reinterpret_cast<celleq::Cells*>(base + dq_freq::kMatchHeadBytes);
+  DQ_HIP(hipMemsetAsync(d_counts, 0, 4 * sizeof(unsigned long long), f->stream));
+  if (n_pairs > 0)
+    DQ_HIP(hipMemcpyAsync(d_cells, cells.data(), cells.size() * sizeof(celleq::Cells), hipMemcpyHostToDevice, f->stream));
+  uint64_t* matched = static_cast<uint64_t*>(f->d_probe.ptr);
+  DQ_HIP(launch_freq_match_rows(f->ks, static_cast<const DevColumn*>(f->d_cols.ptr), n_rows, f->view(), d_selected,
+                                follow ? static_cast<const long long*>(f->d_row_of_slot.ptr) : nullptr, b_rows, d_cells,
+                                d_cells + n_pairs, n_pairs, matched, reinterpret_cast<long long*>(d_reference_rows),
+                                d_counts, f->stream));
+  DQ_HIP(launch_rows_combine(nullptr, matched, d_selected, n_rows, out_bit_offset, d_value, d_valid, f->stream));
+  unsigned long long got[4] = {0, 0, 0, 0};
+  DQ_HIP(hipMemcpyAsync(got, d_counts, sizeof(got), hipMemcpyDeviceToHost, f->stream));
+  DQ_HIP(hipStreamSynchronize(f->stream));
+  f->host_tmp.clear();
+  if (counts) {
+    counts->matched += (int64_t)got[0];
+    counts->key_null += (int64_t)got[1];
+    counts->key_absent += (int64_t)got[2];
+    counts->cells_differ += (int64_t)got[3];
+  }
   return DQ_OK;
 }
 

@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "../../include/deequ_amd.h"
+#include "dq_celleq.h"
 
 namespace dq {
 
@@ -398,6 +399,23 @@ hipError_t launch_freq_linf(const FreqTable& X, const FreqTable& Y, double nx, d
 constexpr int64_t kFreqProbeMaxBlocks = 2048;
 hipError_t launch_freq_probe_rows(const FreqKeySpec& ks, const DevColumn* d_cols, int64_t n_rows, const FreqTable& T,
                                   uint64_t* d_unique, long long* d_counts, hipStream_t stream);
+// Cross-table checks (dq_freq_index_rows / dq_freq_match_rows, dq_freq.hip "Cross-table checks").
+// index: d_row_of_slot[slot of row r's key] = row_offset + r for every row of the batch with a key
+// (one int64 per slot of T, -1 where no row was indexed); *d_absent += the rows whose key T does not
+// hold.  match: bit r of d_matched (ceil(n_rows / 64) words, bits at and past n_rows 0) = row r's
+// key is in T and, with compare pairs, every pair is NULL-safe equal between row r of d_a_cmp[p] and
+// row d_row_of_slot[slot] of d_b_cmp[p] (device arrays of n_pairs columns; rows of B in [0, b_rows));
+// d_reference_rows[r] (nullptr: not wanted) = that row of B or -1; d_counts[0..3] += the TRUE /
+// NULL-key / absent-key / differing rows among d_selected (nullptr: every row).  d_row_of_slot may
+// be nullptr only with no pair and no d_reference_rows.  The probe's geometry.
+hipError_t launch_freq_index_rows(const FreqKeySpec& ks, const DevColumn* d_cols, int64_t n_rows, const FreqTable& T,
+                                  long long* d_row_of_slot, int64_t row_offset, unsigned long long* d_absent,
+                                  hipStream_t stream);
+hipError_t launch_freq_match_rows(const FreqKeySpec& ks, const DevColumn* d_cols, int64_t n_rows, const FreqTable& T,
+                                  const uint64_t* d_selected, const long long* d_row_of_slot, int64_t b_rows,
+                                  const celleq::Cells* d_a_cmp, const celleq::Cells* d_b_cmp, int n_pairs,
+                                  uint64_t* d_matched, long long* d_reference_rows, unsigned long long* d_counts,
+                                  hipStream_t stream);
 // dq_rows.hip.  combine: value = condition & selected, valid = selected over n_rows rows, written
 // at bit out_off of the two bitmaps (the other bits of the edge words are kept).  The condition is
 // a byte-aligned Arrow bitmap at bit 0 (cond_bytes: a column's validity), else 64-bit words

@@ -868,6 +868,46 @@ dq_status dq_freq_probe_rows(dq_freq* f, const dq_column* columns, int n_columns
 dq_status dq_rows_select(dq_ctx* ctx, const uint64_t* d_value, const uint64_t* d_valid, int64_t n_rows, int which,
                          int64_t* d_out, int64_t capacity, int64_t* n_out);
 
+/* ---------------------------------------------------------------- cross-table checks
+ * Referential integrity and dataset match between a primary table A and a reference table B, as
+ * row-level outcomes of A (the bitmap pair above).  The dq_freq is the group-by of B's key columns
+ * (not a DQ_FREQ_NULL_AS_KEY one: DQ_ERR_INVALID); A's key columns are handed to it in the place of
+ * B's (same count, order and types).  A row of A that d_selected does not select is NULL; a
+ * selected row is TRUE iff every key column is non-NULL, the table holds the key, and -- with
+ * compare pairs -- every pair (a_compare[p], b_compare[p]) is NULL-safe equal between that row of A
+ * and the row of B holding the key: NULL equals NULL only; integers, bool and decimal128 by value;
+ * float32 / float64 as Spark's doubles (any NaN equals any NaN, -0.0 equals 0.0); strings by length
+ * and bytes.  Key equality is the group-by's own.
+ *
+ * dq_freq_index_rows records, for every row of a batch of B that has a key, which row holds it:
+ * row_offset + the row's index in the batch, in an int64 per table slot that the handle owns.  The
+ * index lives until the table changes (consume, merge, import, reset), and is built anew by the
+ * first call after that.  The batch must be rows the table was built from: a key the table does not
+ * hold is DQ_ERR_STATE (and drops the index), a filtered table DQ_ERR_INVALID.  With a key in several
+ * rows any one of them stays; dataset match needs unique keys, which dq_freq_get_summary shows
+ * (num_groups == num_unique).
+ *
+ * dq_freq_match_rows writes the outcomes of one batch of A at out_bit_offset, as
+ * dq_freq_probe_rows does, and ADDS the batch's rows to *counts (NULL: not wanted): of the selected
+ * rows, `matched` are TRUE, `key_null` have a NULL key column, `key_absent` a key the table (or,
+ * when the index is followed, its indexed rows) does not hold, `cells_differ` a compare pair that
+ * differs; the four sum to the selected rows.  The compare columns are DQ_COL_DEVICE columns of
+ * equal type per pair, read in place at their `offset`: a_compare over the batch's n_rows rows,
+ * b_compare over all b_rows rows of B (the rows the index numbers).  At most DQ_MATCH_MAX_PAIRS
+ * pairs (more: DQ_ERR_UNSUPPORTED).  d_reference_rows (NULL: not wanted) receives, per row of the
+ * batch and whatever d_selected says, the row of B holding its key, or -1.  Compare pairs and
+ * d_reference_rows follow the index (DQ_ERR_STATE without one); with neither, the index is not
+ * needed and not read, so the table may be a loaded or merged state of the reference keys. */
+#define DQ_MATCH_MAX_PAIRS 32
+typedef struct dq_match_counts {
+  int64_t matched, key_null, key_absent, cells_differ;
+} dq_match_counts;
+dq_status dq_freq_index_rows(dq_freq* f, const dq_column* columns, int n_columns, int64_t n_rows, int64_t row_offset);
+dq_status dq_freq_match_rows(dq_freq* f, const dq_column* columns, int n_columns, int64_t n_rows,
+                             const uint64_t* d_selected, int64_t out_bit_offset, uint64_t* d_value, uint64_t* d_valid,
+                             const dq_column* a_compare, const dq_column* b_compare, int n_pairs, int64_t b_rows,
+                             int64_t* d_reference_rows, dq_match_counts* counts);
+
 #ifdef __cplusplus
 }
 #endif

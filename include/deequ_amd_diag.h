@@ -58,6 +58,12 @@ dq_status dq_diag_parse_double(const uint8_t* s, int64_t n, double* out, int32_t
 dq_status dq_diag_eval_predicate(const dq_predicate* p, const dq_column* columns, int n_columns, int64_t n_rows,
                                  uint8_t* out);
 
+/* Host build of the cross-table checks' NULL-safe cell equality (the source dq_freq_match_rows runs
+ * on the device, deequ_amd/csrc/dq_celleq.h): *equal = row i of `a` <=> row j of `b`, two HOST
+ * columns of one type, read at their `offset`.  DQ_ERR_INVALID for two types or a row outside a
+ * column. */
+dq_status dq_diag_cell_equal(const dq_column* a, int64_t i, const dq_column* b, int64_t j, int32_t* equal);
+
 /* Host build of the group-by's record packing of digit-string keys (<= 15 ASCII digits, or
  * Histogram's "NullValue"; deequ_amd/csrc/dq_keypack.h): *ok = 1, *packed = the 8-byte record
  * word and back[0 .. *back_len) = the key bytes it unpacks to; *ok = 0 for any other key. */
