@@ -36,6 +36,7 @@ from .arrow import ArrowBatch, ArrowTable
 from .table import Column, PartitionedTable, Table
 from .rowlevel import RowLevelResults, row_level_results
 from .comparison import MatchCounts, MatchResult, dataset_match, referential_integrity
+from .take import take
 from .schema import RowLevelSchema, RowLevelSchemaValidationResult, RowLevelSchemaValidator
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -218,6 +218,7 @@ DIAG_SIGNATURES = {
     "dq_diag_mi_from_fixed": (c_int, [c_uint64, c_int64, POINTER(c_double)]),
     "dq_diag_plan_groups": (c_int, [c_void_p, POINTER(c_int64), c_int32, POINTER(c_int32), POINTER(c_int64)]),
     "dq_diag_plan_lanemask": (c_int, [c_void_p, POINTER(c_int32), c_int32, POINTER(c_int32)]),
+    "dq_diag_take_constants": (c_int, [POINTER(c_int64)]),
 }
 
 
@@ -332,6 +333,12 @@ SIGNATURES = {
     "dq_freq_match_rows": (c_int, [c_void_p, POINTER(DqColumn), c_int, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
                                    POINTER(DqColumn), POINTER(DqColumn), c_int, c_int64, c_void_p,
                                    POINTER(DqMatchCounts)]),
+    "dq_take_create": (c_int, [c_void_p, c_void_p, c_int64, POINTER(c_int64), c_int, POINTER(c_void_p)]),
+    "dq_take_info": (c_int, [c_void_p, POINTER(c_int64)]),
+    "dq_take_layout": (c_int, [c_void_p, POINTER(DqColumn), POINTER(c_int32), POINTER(c_int64), POINTER(c_int64),
+                               POINTER(c_int64)]),
+    "dq_take_gather": (c_int, [c_void_p, POINTER(DqColumn), c_void_p, c_void_p, c_void_p]),
+    "dq_take_destroy": (c_int, [c_void_p]),
 }
 
 _lib = None
@@ -434,6 +441,14 @@ def diag_plan_match_tasks(plan_handle):
     t, i = c_int32(0), c_int32(0)
     check(lib().dq_diag_plan_match_tasks(plan_handle, ctypes.byref(t), ctypes.byref(i)))
     return t.value, i.value
+
+
+def diag_take_constants():
+    """dq_diag_take_constants: {"rows_per_block", "scan_tile", "wave_bytes", "split_bytes"} of take's
+    kernels (deequ_amd/csrc/dq_take.h)."""
+    out = (c_int64 * 4)()
+    check(lib().dq_diag_take_constants(out))
+    return dict(zip(("rows_per_block", "scan_tile", "wave_bytes", "split_bytes"), out[:4]))
 
 
 def device_count() -> int:

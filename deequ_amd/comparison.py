@@ -83,6 +83,21 @@ class MatchResult:
             raise KeyError("no reference rows were kept: ask with reference_rows=True")
         return self._reference_rows if self._rows.on_device else self._reference_rows.cpu()
 
+    def take(self, primary, which: str = "false", columns=None) -> Table:
+        """The rows of `primary` whose outcome is `which`, as a Table in row order."""
+        return self._rows.take(primary, _OUTCOME, which, columns)
+
+    def mismatches(self, primary, reference, columns=None, reference_columns=None) -> Tuple[Table, Table]:
+        """(a_rows, b_rows), two tables of equal length: the failing rows of `primary` and, row for
+        row, the row of `reference` holding that key -- an all-NULL row where no row holds it.  Needs
+        the reference rows (`reference_rows=True`)."""
+        from .take import take
+        if self._reference_rows is None:
+            self.reference_rows()  # (raises the KeyError)
+        rows = self._rows.rows(_OUTCOME, "false").to(self._reference_rows.device)
+        a_rows = self._rows.take(primary, _OUTCOME, "false", columns)
+        return a_rows, take(reference, self._reference_rows[rows], reference_columns)
+
 
 # ---------------------------------------------------------------- argument checks (no device)
 def _pairs(items, what: str) -> List[Tuple[str, str]]:

@@ -32,6 +32,7 @@
 #include "dq_kll.h"
 #include "dq_quantile.h"
 #include "dq_schema.h"
+#include "dq_take.h"
 #include "../../include/deequ_amd_diag.h"
 #include "hll_p9_tables.h"
 
@@ -2869,3 +2870,6 @@ extern "C" dq_status dq_profile_few_strings(dq_ctx* ctx, int32_t n, const dq_col
 
 // Row-level outcomes (dq_rows_*) over the predicate interpreter, the match masks and dq_rows.hip.
 #include "dq_rows_api.inc"
+
+// take (dq_take_*): rows of chunked device columns gathered by index, over the kernels of dq_take.hip.
+#include "dq_take_api.inc"

@@ -147,6 +147,43 @@ class RowLevelResults:
         """The ascending indices of the rows the analyzer selects and does not count (FALSE)."""
         return self.rows(analyzer, "false")
 
+    def _check_data(self, data, what: str) -> None:
+        if data.count() != self.num_rows:
+            raise ValueError("%s: the outcomes cover %d rows, the table has %d (hand in the data they were computed "
+                             "over)" % (what, self.num_rows, data.count()))
+
+    def take(self, data, analyzer, which: str = "false", columns=None):
+        """The rows of `data` (the table the outcomes were computed over) whose outcome of
+        `analyzer` is `which`, as a Table in row order (deequ_amd/take.py): by default the failing
+        records themselves."""
+        from .take import take
+        self._pair(analyzer)
+        if which not in _WHICH:
+            raise ValueError("which is \"false\", \"true\" or \"null\", not %r" % (which,))
+        self._check_data(data, "RowLevelResults.take")
+        return take(data, self.rows(analyzer, which), columns)
+
+    def split(self, data, analyzers=None, columns=None):
+        """(passing, failing): `failing` holds the rows that are FALSE for at least one of
+        `analyzers` (default: all of them), `passing` every other row -- a NULL outcome passes: a row
+        its `where` does not select is not a failure.  Both keep the input order, and their row
+        counts sum to num_rows.  The FALSE planes are OR-ed as 64-bit words in HBM and the two row
+        lists selected by dq_rows_select."""
+        import torch
+        from .take import take
+        analyzers = self.analyzers if analyzers is None else list(analyzers)
+        self._check_data(data, "RowLevelResults.split")
+        dev = torch.device("cuda", self.device)
+        words = max(1, bitmap_words(self.num_rows))
+        failing = torch.zeros(words, dtype=torch.int64, device=dev)
+        for a in analyzers:
+            value, valid = self._pair(a)
+            failing |= ~value & valid
+        ones = torch.full((words,), -1, dtype=torch.int64, device=dev)
+        torch.cuda.synchronize(dev)
+        both = RowLevelResults(self.num_rows, self.device, True, {"failing": (failing, ones)})
+        return (take(data, both.rows("failing", "false"), columns), take(data, both.rows("failing", "true"), columns))
+
 
 # ---------------------------------------------------------------- evaluation
 class _ScanRows:

@@ -908,6 +908,42 @@ dq_status dq_freq_match_rows(dq_freq* f, const dq_column* columns, int n_columns
                              const dq_column* a_compare, const dq_column* b_compare, int n_pairs, int64_t b_rows,
                              int64_t* d_reference_rows, dq_match_counts* counts);
 
+/* ---------------------------------------------------------------- take
+ * The rows of a table named by row indices, as new columns in buffers the caller owns: what turns
+ * the row numbers of dq_rows_select and d_reference_rows into records.  A column is n_chunks
+ * DQ_COL_DEVICE dq_columns of one type (the batches of a partitioned table), chunk c holding
+ * chunk_rows[c] rows; d_rows (a device array of m int64) numbers the rows of their concatenation
+ * from 0, in any order and with repeats.  -1 means "no row": every column's output cell is NULL.
+ * Any other value outside [-1, total rows) makes dq_take_create return DQ_ERR_INVALID, with the
+ * first offending position and its value in dq_last_error.  The indices are checked, and mapped to
+ * (chunk, local row), once, in a pass that reads only d_rows; the handle keeps the map for every
+ * column and no longer reads d_rows.  n_chunks is 1..4096 (more: DQ_ERR_UNSUPPORTED); m = 0 is
+ * valid and gives empty outputs.
+ *
+ * Per column: dq_take_layout sizes the output, the caller allocates device buffers of those sizes
+ * (0: the buffer is absent and its pointer may be NULL), and dq_take_gather -- with the same
+ * chunks -- fills them: Arrow layout at offset 0, in the order of d_rows.  Types: bool, int8..int64,
+ * float32, float64, every decimal(p,s) (16-byte cells) and utf8.  A chunk's `offset` is honoured
+ * for values, for bit buffers at any bit offset and for utf8 offsets; a utf8 heap need not start at
+ * its byte 0.  Bit buffers (bool values, validity) are whole 64-bit words, the bits past m 0, and
+ * need 8-byte aligned outputs; value buffers their width's alignment.  validity_bytes is 0 when no
+ * chunk has a validity buffer and no index is -1.  A fixed-width NULL cell holds its source's bytes
+ * (a -1 cell zeros); a utf8 NULL cell has length 0 whatever offsets the source gives it, and its
+ * source bytes are never read.  utf8 output offsets are int32: when the gathered bytes exceed
+ * INT32_MAX, dq_take_layout returns DQ_ERR_SPACE with the total in dq_last_error (the lengths are
+ * summed in 64 bits) before any byte is copied.  A host-resident chunk, a chunk of another type
+ * or row count is DQ_ERR_INVALID.  Calls are synchronous and, per handle, not thread-safe. */
+typedef struct dq_take dq_take;
+dq_status dq_take_create(dq_ctx* ctx, const int64_t* d_rows, int64_t m, const int64_t* chunk_rows, int n_chunks,
+                         dq_take** out);
+/* *n_null_rows = how many of the m indices are -1. */
+dq_status dq_take_info(dq_take* take, int64_t* n_null_rows);
+dq_status dq_take_layout(dq_take* take, const dq_column* chunks, int32_t* type, int64_t* values_bytes,
+                         int64_t* validity_bytes, int64_t* offsets_bytes);
+/* The column dq_take_layout was last called for (anything else: DQ_ERR_STATE). */
+dq_status dq_take_gather(dq_take* take, const dq_column* chunks, void* values, void* validity, void* offsets);
+dq_status dq_take_destroy(dq_take* take);
+
 #ifdef __cplusplus
 }
 #endif

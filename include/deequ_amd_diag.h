@@ -168,6 +168,12 @@ dq_status dq_diag_plan_groups(dq_plan* plan, int64_t* groups, int32_t capacity, 
  * and before the first batch). */
 dq_status dq_diag_plan_lanemask(dq_plan* plan, int32_t* tasks, int32_t capacity, int32_t* n_tasks);
 
+/* The tiling constants of take (deequ_amd/csrc/dq_take.h), from which tests derive their shapes:
+ * out[0] = output rows per workgroup, out[1] = entries per tile of the offsets' scan, out[2] = the
+ * cell length from which a wave, not a lane, copies a utf8 cell, out[3] = the length from which a
+ * cell is cut into pieces of that size for workgroups of their own.  `out` holds 4 values. */
+dq_status dq_diag_take_constants(int64_t* out);
+
 #ifdef __cplusplus
 }
 #endif
