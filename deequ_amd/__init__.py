@@ -37,6 +37,7 @@ from .table import Column, PartitionedTable, Table
 from .rowlevel import RowLevelResults, row_level_results
 from .comparison import MatchCounts, MatchResult, dataset_match, referential_integrity
 from .take import take
+from .correlation import CorrelationMatrix, correlation_matrix
 from .schema import RowLevelSchema, RowLevelSchemaValidationResult, RowLevelSchemaValidator
 
 __all__ = [n for n in dir() if not n.startswith("_")]

@@ -219,6 +219,8 @@ DIAG_SIGNATURES = {
     "dq_diag_plan_groups": (c_int, [c_void_p, POINTER(c_int64), c_int32, POINTER(c_int32), POINTER(c_int64)]),
     "dq_diag_plan_lanemask": (c_int, [c_void_p, POINTER(c_int32), c_int32, POINTER(c_int32)]),
     "dq_diag_take_constants": (c_int, [POINTER(c_int64)]),
+    "dq_diag_corrmat_host": (c_int, [POINTER(c_void_p), POINTER(c_void_p), c_void_p, c_int32, c_int64, c_int64,
+                                     c_void_p, c_void_p]),
 }
 
 
@@ -339,6 +341,12 @@ SIGNATURES = {
                                POINTER(c_int64)]),
     "dq_take_gather": (c_int, [c_void_p, POINTER(DqColumn), c_void_p, c_void_p, c_void_p]),
     "dq_take_destroy": (c_int, [c_void_p]),
+    "dq_corrmat_create": (c_int, [c_void_p, POINTER(c_int32), c_int, POINTER(c_int32), c_int, POINTER(DqPredicate),
+                                  POINTER(c_void_p)]),
+    "dq_corrmat_consume": (c_int, [c_void_p, POINTER(DqColumn), c_int, c_int64]),
+    "dq_corrmat_finish": (c_int, [c_void_p, c_void_p, POINTER(c_int64)]),
+    "dq_corrmat_reset": (c_int, [c_void_p]),
+    "dq_corrmat_destroy": (c_int, [c_void_p]),
 }
 
 _lib = None

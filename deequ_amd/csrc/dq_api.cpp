@@ -2873,3 +2873,7 @@ extern "C" dq_status dq_profile_few_strings(dq_ctx* ctx, int32_t n, const dq_col
 
 // take (dq_take_*): rows of chunked device columns gathered by index, over the kernels of dq_take.hip.
 #include "dq_take_api.inc"
+
+// The correlation matrix (dq_corrmat_*): every pairwise Correlation state in one pass, over dq_corrmat.hip
+// and the pair kernel; with its host mirror.
+#include "dq_corrmat_api.inc"

@@ -7,6 +7,7 @@
 
 #include "../../include/deequ_amd.h"
 #include "dq_celleq.h"
+#include "dq_corrmat.h"
 
 namespace dq {
 
@@ -157,14 +158,12 @@ struct MatchSource {
   const uint32_t* offsets;
 };
 
-// Correlation task (dq_pair.hip) and its running state CorrelationState(n, xAvg, yAvg, ck, xMk, yMk).
+// Correlation task (dq_pair.hip); its running state CorrelationState(n, xAvg, yAvg, ck, xMk, yMk) is
+// CorrAcc (dq_corrmat.h, with CorrelationState.sum and the sums -> state conversion).
 struct CorrTask {
   int32_t x, y;
   int32_t where_mask;  // -1 = none
   int32_t pad;
-};
-struct CorrAcc {
-  double n, xavg, yavg, ck, xmk, ymk;
 };
 
 // Decimal scan task (dq_scan_dec.hip): every scan-shareable analyzer of one decimal (column, where)
@@ -657,6 +656,21 @@ hipError_t launch_regex(const RegexTask* d_tasks, int n_tasks, const DevColumn* 
 hipError_t launch_corr(const CorrTask* d_tasks, int n_tasks, const DevColumn* d_cols, const DevMask* d_masks,
                        int64_t n_rows, int blocks_per_task, CorrAcc* d_partials, CorrAcc* d_acc,
                        hipStream_t stream);
+// The correlation matrix (dq_corrmat.hip): the k columns d_sel of d_cols over row ranges of
+// slabs_per_range slabs (n_ranges of them: d_partials holds n_ranges * k (k + 1) / 2 states), then the
+// fixed tree into d_batch[pair] (written, not merged).  masked: some selected column has a validity
+// bitmap or d_where_t (the filter's TRUE words, or nullptr) is set.  d_pair_flags[pair] / d_col_flags[i]
+// (zeroed by the caller) are raised (pairs: kCorrmatCancel | kCorrmatNonFinite) for what the matrix sums do not answer (dq_corrmat.h).
+hipError_t launch_corrmat(bool masked, const DevColumn* d_cols, const int32_t* d_sel, int k, const uint64_t* d_where_t,
+                          int64_t n_rows, int64_t slabs_per_range, int n_ranges, CorrAcc* d_partials, CorrAcc* d_batch,
+                          uint32_t* d_pair_flags, uint32_t* d_col_flags, hipStream_t stream);
+// Spark's per-row update over the tasks' rows (the pairs whose sums of finite values were not finite):
+// d_partials holds n_tasks * blocks_per_task states, d_out[task] is written (not merged).
+hipError_t launch_corrmat_rows(const CorrTask* d_tasks, int n_tasks, const DevColumn* d_cols, const DevMask* d_masks,
+                               int64_t n_rows, int blocks_per_task, CorrAcc* d_partials, CorrAcc* d_out, hipStream_t stream);
+// d_running[p] += d_fallback[d_fb_index[p]] where d_fb_index[p] >= 0 (nullptr: nowhere), else d_batch[p].
+hipError_t launch_corrmat_combine(const CorrAcc* d_batch, const CorrAcc* d_fallback, const int32_t* d_fb_index,
+                                  int64_t n_pairs, CorrAcc* d_running, hipStream_t stream);
 hipError_t launch_cast_utf8(const DevColumn& src, int64_t n_rows, int to_type, void* d_values, uint8_t* d_validity,
                             hipStream_t stream);
 // The decimal scan (dq_scan_dec.hip): grid (blocks_per_task, n_tasks), partial of (task i, block b)

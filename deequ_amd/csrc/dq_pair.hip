@@ -15,7 +15,7 @@
 //    xMk = Σdx² - (Σdx)²/n (and ck, yMk alike) is only accurate while the shift lies near the data,
 //    so the shift is the first selected finite pair of the wave's rows however far in that is
 //    (never (0, 0) while the wave has one), and a wave whose sums still cancel (moments_cancel,
-//    dq_scan_common.h: the shift was an outlier) sums its rows again about its own mean.
+//    dq_corrmat.h: the shift was an outlier) sums its rows again about its own mean.
 #include "dq_internal.h"
 #include "dq_scan_common.h"
 
@@ -68,23 +68,7 @@ __device__ inline double as_double(const DevColumn& c, int64_t row) {
   }
 }
 
-// CorrelationState.sum (Correlation.scala:37-52); empty sides are identities.
-__device__ inline void corr_merge(CorrAcc& a, const CorrAcc& b) {
-  if (b.n == 0.0) return;
-  if (a.n == 0.0) {
-    a = b;
-    return;
-  }
-  const double n1 = a.n, n2 = b.n, n = n1 + n2;
-  const double dx = b.xavg - a.xavg, dxn = dx / n;
-  const double dy = b.yavg - a.yavg, dyn = dy / n;
-  a.xavg = a.xavg + dxn * n2;
-  a.yavg = a.yavg + dyn * n2;
-  a.ck = a.ck + b.ck + dx * dyn * n1 * n2;
-  a.xmk = a.xmk + b.xmk + dx * dxn * n1 * n2;
-  a.ymk = a.ymk + b.ymk + dy * dyn * n1 * n2;
-  a.n = n;
-}
+// (CorrelationState.sum, corr_merge, and the sums -> state conversion, corr_from_sums: dq_corrmat.h)
 
 __device__ inline CorrAcc shfl_down_acc(const CorrAcc& a, int d) {
   CorrAcc o;
@@ -185,7 +169,7 @@ __global__ __launch_bounds__(kBlock) void dq_corr_kernel(const CorrTask* __restr
     }
   };
   accumulate();
-  // The cancellation guard (moments_cancel, dq_scan_common.h), on the wave's sums: when the
+  // The cancellation guard (moments_cancel, dq_corrmat.h), on the wave's sums: when the
   // shift is an outlier in x or in y the wave sums its rows again about its own mean.  The cross
   // term needs no test of its own: |Sx * Sy / n| = sqrt(qx * qy) <= kMomentCancel * sqrt(xMk * yMk)
   // once neither side cancels, and ck is judged on that scale.
@@ -204,15 +188,7 @@ __global__ __launch_bounds__(kBlock) void dq_corr_kernel(const CorrTask* __restr
   CorrAcc a;
   a.n = n;
   a.xavg = a.yavg = a.ck = a.xmk = a.ymk = 0.0;
-  if (n > 0.0) {
-    a.xavg = sx + s_x / n;
-    a.yavg = sy + s_y / n;
-    a.ck = s_xy - s_x * s_y / n;
-    a.xmk = s_xx - s_x * s_x / n;
-    a.ymk = s_yy - s_y * s_y / n;
-    a.xmk = a.xmk < 0.0 ? 0.0 : a.xmk;  // rounding; NaN/Inf propagate
-    a.ymk = a.ymk < 0.0 ? 0.0 : a.ymk;
-  }
+  if (n > 0.0) a = corr_from_sums(sx, sy, n, s_x, s_y, s_xx, s_yy, s_xy);
 #pragma unroll
   for (int d = 32; d >= 1; d >>= 1) {
     const CorrAcc o = shfl_down_acc(a, d);

@@ -868,6 +868,33 @@ dq_status dq_freq_probe_rows(dq_freq* f, const dq_column* columns, int n_columns
 dq_status dq_rows_select(dq_ctx* ctx, const uint64_t* d_value, const uint64_t* d_valid, int64_t n_rows, int which,
                          int64_t* d_out, int64_t capacity, int64_t* n_out);
 
+/* ---------------------------------------------------------------- correlation matrix
+ * Every pairwise Correlation(x, y, where) state of up to 64 numeric columns from one pass over the
+ * rows: k columns give k (k + 1) / 2 states, i <= j in the order the columns were selected, row-major
+ * over the upper triangle (pair (i, j) at i k - i (i - 1) / 2 + (j - i)).  A row counts for (x, y)
+ * when x and y are non-NULL and the `where` is TRUE; every value is cast to double as Correlation
+ * casts it.  The sums run on the fp64 matrix cores over slabs of 1024 rows; a pair that some slab of
+ * a batch cannot answer that way (a selected non-finite value in one of its columns, sums that are
+ * not finite, a shift that is an outlier: DESIGN.md, Correlation matrix) takes its state of that
+ * batch from the pair kernel of DQ_OP_CORRELATION, over the same rows (finite values whose sums
+ * overflow: from Spark's per-row update).  Batches accumulate in call
+ * order with CorrelationState.sum; the states are bitwise reproducible on one device.
+ *
+ * Call sequence: dq_corrmat_create, dq_corrmat_consume per batch (synchronous), dq_corrmat_finish;
+ * dq_corrmat_reset starts over with the same columns and filter.  Not thread-safe. */
+typedef struct dq_corrmat dq_corrmat;
+/* column_types: the batch's schema; columns: the n_selected (1 to 64: more is DQ_ERR_UNSUPPORTED)
+ * distinct numeric columns of the matrix; where: the optional filter (NULL or n_insns = 0: none),
+ * checked as a dq_op's. */
+dq_status dq_corrmat_create(dq_ctx* ctx, const int32_t* column_types, int n_columns, const int32_t* columns,
+                            int n_selected, const dq_predicate* where, dq_corrmat** out);
+dq_status dq_corrmat_consume(dq_corrmat* m, const dq_column* columns, int n_columns, int64_t n_rows);
+/* states: 6 doubles per pair {n, xAvg, yAvg, ck, xMk, yMk}, six zeros for a pair without a row.
+ * *fallback_pairs (may be NULL) = the pair-batches answered by the pair kernel so far. */
+dq_status dq_corrmat_finish(dq_corrmat* m, double* states, int64_t* fallback_pairs);
+dq_status dq_corrmat_reset(dq_corrmat* m);
+dq_status dq_corrmat_destroy(dq_corrmat* m);
+
 /* ---------------------------------------------------------------- cross-table checks
  * Referential integrity and dataset match between a primary table A and a reference table B, as
  * row-level outcomes of A (the bitmap pair above).  The dq_freq is the group-by of B's key columns

@@ -174,6 +174,16 @@ dq_status dq_diag_plan_lanemask(dq_plan* plan, int32_t* tasks, int32_t capacity,
  * cell is cut into pieces of that size for workgroups of their own.  `out` holds 4 values. */
 dq_status dq_diag_take_constants(int64_t* out);
 
+/* Host mirror of one dq_corrmat_consume batch (deequ_amd/csrc/dq_corrmat.h; no GPU): the same
+ * slabs, per-column shifts, guard, fall-back flags and merge order, the sums as plain fp64 loops.
+ * columns[i][r] = row r of selected column i, already cast to double; valid[i][r] = 0 where it is NULL
+ * (valid or valid[i] may be NULL: no NULLs); where[r] = 0 where the filter is not TRUE (NULL: no
+ * filter); max_ranges = the row ranges the slabs are spread over (the kernel's grid; < 1: one per
+ * slab).  states: 6 doubles per pair as dq_corrmat_finish writes them; flags[p] = 1 where pair p is
+ * not answered from the matrix sums (its state then comes from per-slab sums about the slab's means). */
+dq_status dq_diag_corrmat_host(const double* const* columns, const uint8_t* const* valid, const uint8_t* where,
+                               int32_t n_selected, int64_t n_rows, int64_t max_ranges, double* states, uint8_t* flags);
+
 #ifdef __cplusplus
 }
 #endif
