@@ -398,6 +398,65 @@ def check(status: int):
         raise DeequAmdError(status, msg)
 
 
+def device_inputs(columns) -> bool:
+    """True when one of `columns` (Columns, or None) is device-resident: its buffers are torch
+    tensors in HBM that the library reads in place."""
+    return any(getattr(c, "device", False) for c in columns)
+
+
+# How a Plan orders a device batch with torch's current stream (A/B knob DEEQU_AMD_PLAN_ORDER; the
+# measurements are in DESIGN.md, "Stream ordering at the Python boundary"):
+#   "stream"            the plan's stream waits for the current one, then the current one for the scan
+#   "host_then_stream"  the host waits for the current stream, then the current stream for the scan
+PLAN_ORDER = "stream"
+
+
+class StreamOrder:
+    """The ordering of a library call after the work queued on torch's current stream of `device`
+    ("Stream ordering at the Python boundary"): the library launches on streams of its own,
+    which wait for no torch stream, so the kernel that writes an input -- or that still uses the memory
+    of a freshly allocated output -- may not have run yet.  Used only for device-resident inputs or
+    outputs (it imports torch), with the outputs allocated, right before the library call.
+
+    `StreamOrder(device).wait()` (or `after_current_stream(device)`): the host waits for the current
+    stream.  With `stream`, the hipStream_t every launch of an asynchronous call is ordered on, no host
+    waits: `wait()` makes that stream wait for the current one (nothing at all when the current stream
+    is idle) and returns it, and `release(current)` after the call makes the current stream wait for
+    the call's kernels, so work queued there from then on may overwrite or free the call's inputs.  A
+    handle keeps one StreamOrder: the torch stream and the event are made once, and `release` runs
+    while the device already works on the call."""
+
+    def __init__(self, device: int, stream: int = 0):
+        self.device, self.stream = device, stream
+        self._own = self._event = None
+        self.mode = os.environ.get("DEEQU_AMD_PLAN_ORDER", PLAN_ORDER) if stream else "host"
+
+    def wait(self):
+        import torch
+        current = torch.cuda.current_stream(self.device)
+        if self.mode != "stream":
+            current.synchronize()
+            if self.mode == "host" or self._own is not None:
+                return current
+        if self._own is None:
+            self._own = torch.cuda.ExternalStream(self.stream, device=torch.device("cuda", self.device))
+            self._event = torch.cuda.Event()
+        if self.mode == "stream" and not current.query():
+            self._event.record(current)
+            self._own.wait_event(self._event)
+        return current
+
+    def release(self, current) -> None:
+        if self.mode == "stream" or self.mode == "host_then_stream":
+            self._event.record(self._own)
+            current.wait_event(self._event)
+
+
+def after_current_stream(device: int) -> None:
+    """The host waits for torch's current stream of `device` (StreamOrder)."""
+    StreamOrder(device).wait()
+
+
 PLAN_LAUNCHES = ("regex", "string_pass", "hll", "datatype", "strlen", "corr", "dec")
 
 

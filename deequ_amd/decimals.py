@@ -48,6 +48,8 @@ def cast_to_float64(column, device: int):
     values = torch.empty(max(1, n), dtype=torch.float64, device=dev)
     validity = torch.zeros(max(1, (n + 7) // 8) + 8, dtype=torch.uint8, device=dev)
     src = column.to_dq()
+    # the library's stream waits for no torch stream: the column is there and the validity is zeroed
+    L.after_current_stream(device)
     L.check(L.lib().dq_cast_decimal(L.Context.get(device).handle, ctypes.byref(src), n, values.data_ptr(),
                                     validity.data_ptr()))
     return Column("float64", n, values, validity, device=True)

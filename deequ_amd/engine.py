@@ -195,6 +195,7 @@ class Plan:
                                        ctypes.byref(h)))
         self.handle = h
         self._out = (L.DqState * max(1, self.n_ops))()
+        self._order = None  # (a device batch's ordering with torch's current stream, made at the first one)
 
     def consume(self, batch) -> None:
         from .arrow import ArrowBatch
@@ -204,7 +205,19 @@ class Plan:
             L.check(L.lib().dq_plan_consume_arrow(self.handle, ctypes.byref(schema), ctypes.byref(array), 0))
             return
         cols = dq_columns(batch, self.names)
-        L.check(L.lib().dq_plan_consume(self.handle, cols, len(self.names), batch.num_rows))
+        # dq_plan_consume only queues the scan, on the plan's stream: for a batch in HBM that stream
+        # waits for the batch's producers on torch's current stream, and the current stream then for
+        # the scan -- the caller may overwrite or free the batch right away
+        if not L.device_inputs(batch.columns[n] for n in self.names):
+            L.check(L.lib().dq_plan_consume(self.handle, cols, len(self.names), batch.num_rows))
+            return
+        if self._order is None:
+            self._order = L.StreamOrder(self.device, self.stream)
+        current = self._order.wait()
+        try:
+            L.check(L.lib().dq_plan_consume(self.handle, cols, len(self.names), batch.num_rows))
+        finally:
+            self._order.release(current)
 
     def finish_raw(self):
         L.check(L.lib().dq_plan_finish(self.handle, self._out, self.n_ops))

@@ -148,6 +148,8 @@ class FrequencyTable:
             L.check(L.lib().dq_freq_consume_arrow(self.handle, ctypes.byref(schema), ctypes.byref(array), 0))
             return
         cols = dq_columns(batch, self.names)
+        if L.device_inputs(batch.columns[n] for n in self.names):
+            L.after_current_stream(self.device)  # the table's stream waits for no torch stream: the batch is there
         L.check(L.lib().dq_freq_consume(self.handle, cols, len(self.names), batch.num_rows))
 
     def summary(self) -> L.DqFreqSummary:
@@ -173,6 +175,7 @@ class FrequencyTable:
             offs = torch.empty(n.value + 1, dtype=torch.int64, device=self.torch_device)
             blob = torch.empty(max(1, kb.value), dtype=torch.uint8, device=self.torch_device)
             ptrs = (counts.data_ptr(), offs.data_ptr(), blob.data_ptr())
+            L.after_current_stream(self.device)  # (nothing queued there still uses the memory the outputs took)
         else:
             counts = np.empty(max(1, n.value), dtype=np.int64)
             offs = np.empty(n.value + 1, dtype=np.int64)
@@ -200,6 +203,11 @@ class FrequencyTable:
             c = counts.to(torch.int64).contiguous()
             o = offsets.to(torch.int64).contiguous()
             b = blob.to(torch.uint8).contiguous()
+            # the conversions above and the caller's producers are queued on torch's current stream,
+            # the library reads on the table's: wait for them.  dq_freq_import_flat reads the
+            # table's counters back after its kernel (check_overflow), so c, o and b have been read
+            # when it returns and may go back to torch's allocator
+            L.after_current_stream(self.device)
             L.check(L.lib().dq_freq_import_flat(self.handle, c.data_ptr(), o.data_ptr(), b.data_ptr() if b.numel() else None,
                                                 n, int(num_rows), L.DQ_FLAT_DEVICE))
             return

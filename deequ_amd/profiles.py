@@ -149,6 +149,39 @@ def _java_long(x: float) -> int:
     return int(x)  # Double.toLong truncates toward zero
 
 
+def _in_hbm(data) -> bool:
+    """True when a batch of `data` (a ShardedTable: of this rank's shard) holds a device-resident column."""
+    from .distributed import is_sharded
+    from .table import Table
+    local = data.local if is_sharded(data) else data
+    return any(isinstance(b, Table) and L.device_inputs(b.columns.values()) for b in local.batches())
+
+
+def _after_producers(data) -> None:
+    """Called by the public entry points on the caller's thread, before the passes fan out over host
+    threads: torch's current stream is a per-thread setting, so the wait for the producers of a table
+    in HBM (_lib.after_current_stream) cannot be left to the workers."""
+    from .engine import current_device
+    if _in_hbm(data):
+        L.after_current_stream(current_device())
+
+
+def _worker_stream(device: int) -> None:
+    """A worker thread's initializer: the thread gets a stream of torch's pool as its current
+    stream.  A worker's default would be the null stream, shared with every other thread, and the
+    waits that tie a plan to the current stream (Plan.consume) would then chain the workers' scans
+    one behind the other through it."""
+    import torch
+    torch.cuda.set_stream(torch.cuda.Stream(device=device))
+
+
+def _workers(data, device: int) -> dict:
+    """ThreadPoolExecutor arguments for threads that scan `data`: `_worker_stream` for a table in
+    HBM, nothing for a host table (its workers hand the library no device tensor, and no torch call
+    is made for it)."""
+    return {"initializer": _worker_stream, "initargs": (device,)} if _in_hbm(data) else {}
+
+
 class ColumnProfiler:
     DEFAULT_CARDINALITY_THRESHOLD = DEFAULT_CARDINALITY_THRESHOLD
 
@@ -161,6 +194,7 @@ class ColumnProfiler:
         # up to the interpreter's switch interval (5 ms by default) -- on the critical path of a
         # 40 ms profile -- so the interval is shortened for the run and restored afterwards
         # (DEEQU_AMD_PROFILE_SWITCH_US, 0 = leave it).
+        _after_producers(data)
         us = float(os.environ.get("DEEQU_AMD_PROFILE_SWITCH_US", "200"))
         old = sys.getswitchinterval()
         if us > 0:
@@ -245,7 +279,8 @@ class ColumnProfiler:
                     return fn(*args)
                 finally:
                     LAUNCH_GATE.reset(token)
-            pool = ThreadPoolExecutor(max_workers=3)
+            from .engine import current_device
+            pool = ThreadPoolExecutor(max_workers=3, **_workers(data, current_device()))
             bools = [c for c in relevant if schema[c] == "bool" and _IDENT.match(c)]
             started = {}
 
@@ -306,10 +341,12 @@ class ColumnProfiler:
         known = {c: few_hist[c] if c in few_hist else few[c].histogram() for c in targets if c in few}
         known.update({c: bool_hist[c] for c in targets if c in bool_hist})
         todo = [c for c in targets if c not in known]
-        side = ThreadPoolExecutor(max_workers=1) if overlap and todo and not sharded else None
+        from .engine import current_device
+        side = (ThreadPoolExecutor(max_workers=1, **_workers(data, current_device()))
+                if overlap and todo and not sharded else None)
         if side and printStatusUpdates:
             print("### PROFILING: Computing histograms of low-cardinality columns in pass (3/3), beside pass 2...")
-        pending = (side.submit(compute_histograms, data, targets, generic.approximateNumDistincts, known)
+        pending = (side.submit(_histograms, data, targets, generic.approximateNumDistincts, known)
                    if side else None)
         try:
             if casted is None:
@@ -353,7 +390,7 @@ class ColumnProfiler:
             finally:
                 side.shutdown(wait=True)
         else:
-            histograms = compute_histograms(data, targets, generic.approximateNumDistincts, known)
+            histograms = _histograms(data, targets, generic.approximateNumDistincts, known)
         return _create_profiles(relevant, generic, numeric, histograms)
 
 
@@ -428,6 +465,8 @@ def _few_group_strings(data, columns: Sequence[str], before_launch=None) -> Dict
         keys = np.zeros(n * L.DQ_FEW_MAX_GROUPS * 16, dtype=np.uint8)
         lens = np.zeros(n * L.DQ_FEW_MAX_GROUPS, dtype=np.int32)
         cols = (L.DqColumn * n)(*[batch.columns[c].to_dq() for c in live])
+        if L.device_inputs(batch.columns[c] for c in live):
+            L.after_current_stream(ctx.device)  # the library's streams wait for no torch stream: the batch is there
         if before_launch is not None:  # (once: the caller's other threads start here, while the
             before_launch()            # library call below holds no GIL)
             before_launch = None
@@ -484,6 +523,9 @@ def cast_string_column(col, to_dtype: str, device: Optional[int] = None):
     valid = torch.empty((n + 7) // 8 + 8, dtype=torch.uint8, device=dev)
     unsupported = ctypes.c_int64()
     src = col.to_dq()
+    # the library's stream waits for no torch stream: the column is there, and nothing queued on
+    # the current stream still uses the memory the outputs took (dq_cast_utf8 waits for its kernel)
+    L.after_current_stream(dev_idx)
     L.check(L.lib().dq_cast_utf8(L.Context.get(dev_idx).handle, ctypes.byref(src), n, L.TYPE_CODES[to_dtype],
                                  vals.data_ptr(), valid.data_ptr(), ctypes.byref(unsupported)))
     return Column(to_dtype, n, vals, valid, device=True)
@@ -512,6 +554,7 @@ def cast_string_columns(cols, to_dtypes, device: Optional[int] = None):
     types = (ctypes.c_int32 * n)(*[L.TYPE_CODES[t] for t in to_dtypes])
     vptr = (ctypes.c_void_p * n)(*[v.data_ptr() for v, _ in outs])
     bptr = (ctypes.c_void_p * n)(*[b.data_ptr() for _, b in outs])
+    L.after_current_stream(dev_idx)  # as in cast_string_column
     L.check(L.lib().dq_cast_utf8_batch(L.Context.get(dev_idx).handle, n, srcs, rows, types, vptr, bptr))
     return [Column(t, rows, v, b, device=True) for t, (v, b) in zip(to_dtypes, outs)]
 
@@ -612,6 +655,12 @@ def compute_histograms(data, target_columns: Sequence[str],
     """computeHistograms (:564-606): exact (column, value.toString) counts, NULL -> "NullValue",
     one GPU group-by per target column; ratio = count / (sum of the column's counts).  `known`:
     histograms already computed (pass 1's few-groups string columns)."""
+    _after_producers(data)
+    return _histograms(data, target_columns, expected_groups, known)
+
+
+def _histograms(data, target_columns, expected_groups=None, known=None) -> Dict[str, Distribution]:
+    """compute_histograms once the table's producers have been waited for."""
     from .frequencies import FrequencyTable
     schema = data.schema
     out = dict(known or {})
@@ -654,7 +703,7 @@ def compute_histograms(data, target_columns: Sequence[str],
     # few groups, LDS pre-aggregation), and beside them the boolean columns' fused scan (its own
     # plan and stream).  Results are per column, so the order does not matter.
     from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(max_workers=min(len(rest) + (1 if bool_cols else 0), 8)) as ex:
+    with ThreadPoolExecutor(max_workers=min(len(rest) + (1 if bool_cols else 0), 8), **_workers(data, device)) as ex:
         bools = ex.submit(_bool_histograms, data, bool_cols) if bool_cols else None
         for c, dist in zip(rest, ex.map(one, rest)):
             out[c] = dist

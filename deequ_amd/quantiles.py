@@ -47,6 +47,8 @@ class QuantileSketcher:
             L.check(L.lib().dq_aq_consume(self.handle, arr, len(cols), rows))
             return
         cols = dq_columns(batch, self.names)
+        if L.device_inputs(batch.columns[n] for n in self.names):
+            L.after_current_stream(self.device)  # the library's launches wait for no torch stream: the batch is there
         L.check(L.lib().dq_aq_consume(self.handle, cols, len(self.names), batch.num_rows))
 
     def finish(self) -> List[ApproxQuantileState]:

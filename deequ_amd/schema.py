@@ -211,6 +211,7 @@ class _Validator:
                 values = torch.empty(rows, dtype=getattr(torch, dtype), device=dev)
             validity = torch.empty(nb.value, dtype=torch.uint8, device=dev) if nb.value else None
             offsets = torch.empty(ob.value // 4, dtype=torch.int32, device=dev) if ob.value else None
+            L.after_current_stream(self.device)  # (nothing queued there still uses the memory the outputs took)
             L.check(lib.dq_schema_gather(self.handle, which, ci, values.data_ptr() if vb.value else None,
                                          validity.data_ptr() if validity is not None else None,
                                          offsets.data_ptr() if offsets is not None else None))
@@ -226,6 +227,8 @@ class _Validator:
         cols = dq_columns(batch, self.names)
         nv, ni = ctypes.c_int64(), ctypes.c_int64()
         flags = (ctypes.c_int32 * max(1, len(self.defs)))()
+        if L.device_inputs(batch.columns[n] for n in self.names):
+            L.after_current_stream(self.device)  # the library's launches wait for no torch stream: the batch is there
         st = L.lib().dq_schema_validate(self.handle, cols, len(self.names), batch.num_rows, ctypes.byref(nv),
                                         ctypes.byref(ni), flags)
         flagged = [self.defs[i].name for i in range(len(self.defs)) if flags[i]]
